@@ -158,7 +158,9 @@ def synthetic_pairs(B, S, seed, dev, n_events=500000):
     Target: image N(0,1), its ISR from the same kernels, events: `n_events` synthetic events per sample (fractional rectified
     x in [0,640), y in [0,480), sorted t, polarity 0/1) -> voxel-grid kernel (1 bin) -> events_norm -> crop 400x400 -> bilinear
     512x512 -> 3 channels (dsec.py:189-366)."""
+    import random
     from cmda_amd import ops
+    random.seed(seed)   # as loader_pairs does: the step's host draws on python's RNG (uda.DACS._draw) repeat from run to run
     g = torch.Generator().manual_seed(seed)
     image = torch.randn(B, 3, S, S, generator=g).to(dev)
     label_host = synthetic_labels(B, S, g)
@@ -248,6 +250,53 @@ def cpu_baseline_dacs(size):
             'sample': f'1 x (full DACS iteration on 1 source + 1 target pair at {size}x{size}: generator, EMA, source fwd/bwd, '
                       f'teacher, ClassMix/jitter/blur/ISR, mixed fwd/bwd; fp32 oracle/dacs_iter.py) on {cores} host threads '
                       f'after a 64x64 warm-up, {dt:.1f} s per pair'}
+
+
+DUMP_PER_TENSOR = 2048          # --dump-outputs: elements kept of each parameter / gradient / buffer tensor
+DUMP_MAX_BYTES = 64 << 20
+
+
+def tensor_sample(tensors):
+    """A fixed sample of every tensor of `tensors` (model order), concatenated as fp32: the whole tensor up to DUMP_PER_TENSOR
+    elements, else DUMP_PER_TENSOR positions drawn from a generator with a fixed seed -- the same positions in every run, and
+    for every list of tensors of the same shapes (a model's parameters, their gradients, the EMA teacher's)."""
+    g = torch.Generator().manual_seed(0)
+    parts = []
+    for t in tensors:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_PER_TENSOR:
+            flat = flat[torch.randint(0, flat.numel(), (DUMP_PER_TENSOR,), generator=g).to(flat.device)]
+        parts.append(flat.float().cpu())
+    return torch.cat(parts).numpy()
+
+
+def model_outputs(prefix, model):
+    """what a training step leaves in `model`: parameters, their gradients, floating-point buffers (BatchNorm running
+    statistics) -- each as one `tensor_sample`"""
+    params = [p for _, p in model.named_parameters()]
+    out = {f'{prefix}.param': tensor_sample(params),
+           f'{prefix}.buffer': tensor_sample([b for _, b in model.named_buffers() if b.is_floating_point()])}
+    grads = [p.grad for p in params if p.grad is not None]
+    if grads:
+        out[f'{prefix}.grad'] = tensor_sample(grads)
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: DIR/<name>.npy per array, float64 arrays kept, everything else as float32"""
+    import numpy as np
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f'--dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}'
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + '.npy'), v)
+
+
+def log_arrays(log_vars):
+    """the step's logged losses / accuracies as float64 arrays named log_vars.<key>"""
+    return {f'log_vars.{k}': torch.as_tensor(v).detach().double().cpu().numpy() for k, v in log_vars.items()}
 
 
 def profile_json(name):
@@ -429,6 +478,7 @@ def gemm_roofline(step, workload):
 
 
 def run_dacs(args, rank, world, dev, dist):
+    import numpy as np
     from cmda_amd import optim
     from cmda_amd.parallel import GradAllReducer
     B = args.batch if args.batch > 0 else 2   # reference recipe: 2 source + 2 target samples per GPU
@@ -459,6 +509,7 @@ def run_dacs(args, rank, world, dev, dist):
         dacs.final_pass_grad_hook = _ready
     batch = (loader_pairs if args.data == 'loader' else synthetic_pairs)(B, args.size, 100 + rank, dev)
     torch.manual_seed(1000 + rank)            # per-rank DropPath / Dropout / ClassMix streams
+    np.random.seed(1000 + rank)               # ClassMix's class draws (uda.DACS._choose_classes)
     it = [0]
     if not args.no_graph:
         dacs.enable_graph(warmup_iters=2)     # iterations 0-1 eager, iteration 2 captures the hipGraph, then replays
@@ -494,6 +545,9 @@ def run_dacs(args, rank, world, dev, dist):
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if args.dump_outputs and rank == 0:   # the last timed step's results, before the roofline leg runs one more step
+        dump_outputs(args.dump_outputs, dict(log_arrays(lv), **model_outputs('student', dacs.model),
+                                             **model_outputs('teacher', dacs.ema_model)))
     losses = {k: round(float(v), 5) for k, v in lv.items() if 'loss' in k}
     graph_mode = ('linear hipGraph segments replayed on two streams (runtime.SegmentedCapture); EMA update, control-block copy, '
                   'AdamW outside') if dacs._graph is not None else 'eager'
@@ -595,7 +649,7 @@ def run_supervised(args, rank, world, dev, dist):
         reducer.all_reduce_mean()
         opt.step(optim.poly_warm_scale(it[0]))
         it[0] += 1
-        return losses['decode.loss_seg']
+        return losses
 
     def fence():
         if world > 1:
@@ -607,14 +661,16 @@ def run_supervised(args, rank, world, dev, dist):
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        losses = step()
     fence()
     dt = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
-    loss_val = float(loss.item())
+    if args.dump_outputs and rank == 0:   # the last timed step's results, before the roofline leg runs one more step
+        dump_outputs(args.dump_outputs, dict(log_arrays(losses), **model_outputs('model', model)))
+    loss_val = float(losses['decode.loss_seg'].item())
     roofline = gemm_roofline(step, 'supervised') if rank == 0 else None
     if rank == 0:
         ms = dt / args.steps * 1e3
@@ -727,7 +783,14 @@ def main():
     ap.add_argument('--dry-run', action='store_true', help='launch / rendezvous plumbing only (gloo, no GPU work): CPU tests')
     ap.add_argument('--force-reducer', action='store_true',
                     help='testing: run the gradient all-reduce path (RCCL, side stream, staged ranges) even with one rank')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0): the step's losses / accuracies and a "
+                         "fixed sample of the trained model's parameters, gradients and buffers (bench.tensor_sample), at most 64 MB")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_outputs and args.dry_run:
+        ap.error('--dump-outputs needs a real run (a dry run computes nothing)')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` without a launcher: become the launcher.  This process has not touched the GPU (no HIP call,

@@ -391,6 +391,24 @@ def segmentor_train():
         json.dump(sorted(model.state_dict().keys()), f, indent=0)
 
 
+FUSION_CONFIGS = ('cs2dsec_image+events_together_b5', 'cs2dz_image+raw-isr_b5')
+
+
+@case
+def fusion_configs():
+    """the model / uda / data / runner sections that configs/fusion/<name>.py resolve to (its `_base_` chain merged), as JSON:
+    tuples become lists, sets sorted lists (tests/test_registry_config.py, tests/test_datasets.py)"""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from cmda_amd.config import Config
+    os.makedirs(os.path.join(HERE, 'configs'), exist_ok=True)
+    for name in FUSION_CONFIGS:
+        cfg = Config.fromfile(os.path.join(ref_shim.REF, 'configs', 'fusion', name + '.py'))
+        with open(os.path.join(HERE, 'configs', name + '.json'), 'w') as f:
+            json.dump({k: cfg[k] for k in ('model', 'uda', 'data', 'runner')}, f, indent=1, sort_keys=True, default=sorted)
+            f.write('\n')
+        print('wrote', name)
+
+
 def dacs_cfg(G_path):
     """reduced-width FusionEncoderDecoder under the reference's DACS (launcher defaults of SURVEY.md appendix A; DropPath / Dropout
     rates 0 so that the only draws are the ones recorded below)"""

@@ -12,7 +12,7 @@ from cmda_amd import datasets as D
 from cmda_amd.config import Config
 from cmda_amd.registry import DATASETS
 
-REF = '/root/reference/configs/fusion'
+CONFIGS = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'configs')
 SMALL_SRC = dict(raw_size=(256, 128), image_resize_size=(128, 64), image_crop_size=(64, 64), synthetic_length=6)
 
 
@@ -21,11 +21,11 @@ def test_registry_keys_resolve():
         assert key in DATASETS, key
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference configs are only present in the authoring container')
 @pytest.mark.parametrize('name', ['cs2dsec_image+events_together_b5.py', 'cs2dz_image+raw-isr_b5.py'])
 def test_reference_data_configs_build(name):
-    """cfg.data.train / val of the reference's own configs go through build_dataset unchanged (constructor arguments accepted)"""
-    cfg = Config.fromfile(os.path.join(REF, name))
+    """cfg.data.train / val of the reference's own configs go through build_dataset unchanged (constructor arguments accepted;
+    the sections as resolved from the config files: tests/golden/configs/*.json)"""
+    cfg = Config.fromfile(os.path.join(CONFIGS, name[:-len('.py')] + '.json'))
     train = D.build_dataset(cfg.data.train)
     assert type(train).__name__ == 'UDADataset' and len(train) == len(train.source) * len(train.target)
     assert type(train.source).__name__ == 'CityscapesICDataset'

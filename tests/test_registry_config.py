@@ -1,5 +1,6 @@
 """The drop-in boundary: the reference's configs/fusion/*.py load unchanged and every `type` resolves to a cmda_amd
-class with the reference's state_dict keys.  Reads /root/reference (authoring container only; skipped on the GPU box)."""
+class with the reference's state_dict keys.  The two configs are read as the model / uda / data / runner sections their `_base_`
+chains resolve to (tests/golden/configs/*.json, written by tests/golden/make_golden.py::fusion_configs)."""
 import json
 import os
 
@@ -10,8 +11,8 @@ import cmda_amd  # noqa: F401
 from cmda_amd.config import Config, apply_launcher_defaults
 from cmda_amd.registry import MODELS, build_train_model
 
-REF = '/root/reference/configs/fusion'
 HERE = os.path.dirname(os.path.abspath(__file__))
+CONFIGS = os.path.join(HERE, 'golden', 'configs')
 
 
 def test_registry_keys():
@@ -31,10 +32,9 @@ def test_config_merge_semantics(tmp_path):
     assert cfg.lr == 0.2 and cfg.uda.sky_mask is None and cfg.model.head.fusion_cfg.sep is True
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason='reference configs are only present in the authoring container')
 @pytest.mark.parametrize('name', ['cs2dsec_image+events_together_b5.py', 'cs2dz_image+raw-isr_b5.py'])
 def test_reference_fusion_configs_build(name):
-    cfg = apply_launcher_defaults(Config.fromfile(os.path.join(REF, name)))
+    cfg = apply_launcher_defaults(Config.fromfile(os.path.join(CONFIGS, name[:-len('.py')] + '.json')))
     assert cfg.model.type == 'FusionEncoderDecoder' and cfg.uda.type == 'DACS'
     cfg.model.pretrained = None  # pretrained/mit_b5.pth is an external download
     cfg.uda.cyclegan_itrd2en_path = 'random' if cfg.uda.get('cyclegan_itrd2en_path') else ''
