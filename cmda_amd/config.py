@@ -86,10 +86,15 @@ class Config(ConfigDict):
         return self
 
 
-def apply_launcher_defaults(cfg):
+def apply_launcher_defaults(cfg, feature_dist=-1):
     """Keys the reference's launcher injects before tools/train.py sees the config (my_run_experiments.py:97-144,
-    296-299) and that DACS.__init__ expects."""
+    296-299) and that DACS.__init__ expects.  feature_dist: the launcher's --feature_dist (:50, :257-260):
+    != -1 sets uda.imnet_feature_dist_lambda, otherwise a config without the key gets 0."""
     uda = cfg.setdefault('uda', ConfigDict())
+    if feature_dist != -1:
+        uda['imnet_feature_dist_lambda'] = feature_dist
+    else:
+        uda.setdefault('imnet_feature_dist_lambda', 0)
     uda.setdefault('sky_mask', None)
     uda.setdefault('isr_another_fusion', False)
     model = cfg['model']

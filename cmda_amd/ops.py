@@ -961,6 +961,64 @@ def ce_upsample_bwd(logits, label, weight, lse, gscale, gscale_mul, H, W, ignore
     return dl
 
 
+_FD_TICKETS = {}
+
+
+def _fd_ticket(device, slot):
+    """the arrival ticket of a feature-distance launch (zero between launches, see include/cmda_hip.h): one persistent int32 per
+    device and entry point, allocated before any capture sees it"""
+    key = (str(device), slot)
+    t = _FD_TICKETS.get(key)
+    if t is None:
+        t = _FD_TICKETS[key] = torch.zeros(1, dtype=torch.int32, device=device)
+    return t
+
+
+def fdist_label_mask(label, h, w, classes, min_ratio, num_classes=19, ignore_index=255):
+    """downscale_label_ratio (utils/utils.py:18-39) + the class mask of calc_feat_dist (dacs.py:338-345) on the device.  label:
+    int64 [B,H,W] or [B,1,H,W] with H = h*s, W = w*s.  Returns (rescaled int64 [B,h,w], mask uint8 [B,h,w], count int32 [1]) --
+    the count stays on the device."""
+    check_dev(label)
+    B, H, W = label.shape[0], label.shape[-2], label.shape[-1]
+    bits = 0
+    for c in classes:
+        if not 0 <= int(c) < 32:
+            raise L.CmdaError(f'feature-distance class {c} outside 0..31')
+        bits |= 1 << int(c)
+    dev = label.device
+    rescaled = torch.empty(B, h, w, dtype=torch.int64, device=dev)
+    mask = torch.empty(B, h, w, dtype=torch.uint8, device=dev)
+    rows = torch.empty(B * h, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    call('cmda_fdist_label_mask', ptr(label), c_i32(B), c_i32(H), c_i32(W), c_i32(h), c_i32(w), c_i32(num_classes),
+         c_i32(ignore_index), c_f32(min_ratio), ctypes.c_uint32(bits), ptr(rescaled), ptr(mask), ptr(rows), ptr(count),
+         ptr(_fd_ticket(dev, 0)), stream_of(label))
+    return rescaled, mask, count
+
+
+def fdist_fwd_bwd(fs, ft, lam, mask=None, count=None, gscale=None, grad=None):
+    """masked_feat_dist (dacs.py:318-326) times lambda, and its gradient with respect to `fs` ADDED into `grad`.  fs / ft: student /
+    frozen-encoder rows [R, C] in the compute dtype; mask: uint8 [R] (None: every row) with its device count int32 [1]; gscale:
+    fp32 [1] device scale of the gradient (None: 1); grad: [R, C] rows (row stride grad.stride(0)) of fs's dtype (or fp32 under
+    bf16 rows), or None.
+    Returns (loss fp32 [1], per-row norms fp32 [R])."""
+    check_dev(fs, ft, mask, count, gscale)
+    R, C = fs.shape
+    assert ft.shape == fs.shape and ft.dtype == fs.dtype
+    assert (mask is None) == (count is None)
+    if grad is not None:
+        if L.emulated() and grad.is_cuda or (not L.emulated() and not grad.is_cuda):
+            raise L.CmdaError('gradient block on the wrong device')
+        assert grad.shape == fs.shape and grad.stride(1) == 1
+    loss = torch.empty(1, dtype=torch.float32, device=fs.device)
+    norms = torch.empty(R, dtype=torch.float32, device=fs.device)
+    call('cmda_fdist_fwd_bwd', ptr(fs), ptr(ft), ptr(mask), ptr(count), c_i32(R), c_i32(C),
+         c_i64(grad.stride(0) if grad is not None else C), c_f32(lam), ptr(gscale), ptr(grad), ptr(norms), ptr(loss),
+         ptr(_fd_ticket(fs.device, 1)), c_i32(dtype_tag(fs)), c_i32(dtype_tag(grad) if grad is not None else dtype_tag(fs)),
+         stream_of(fs))
+    return loss, norms
+
+
 def pseudo_label(logits, H, W, thr, want_prob=True):
     check_dev(logits)
     B, h, w, nc = logits.shape

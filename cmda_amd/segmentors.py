@@ -217,7 +217,7 @@ class FusionEncoderDecoder(nn.Module):
         feats = {'f_image': f_image, 'f_events': f_events, 'f_fusion': f_fusion, 'f_img_self_res': f_isr}
         return feats, sv, B
 
-    def _extract_bwd(self, sv, dfeats, B):
+    def _extract_bwd(self, sv, dfeats, B, img_grad_hook=None):
         d_img = dfeats.get('f_image')
         d_evt = dfeats.get('f_events')
         d_isr = dfeats.get('f_img_self_res')
@@ -238,7 +238,10 @@ class FusionEncoderDecoder(nn.Module):
                     d_evt = _sum_grads(d_evt, de)
         as_list = lambda d: [d.get(i) for i in range(4)] if isinstance(d, dict) else d
         if 'image' in sv and d_img is not None:
-            self.backbone_image.bwd(sv['image'], as_list(d_img))
+            d_img = as_list(d_img)
+            if img_grad_hook is not None:   # extra terms on the image encoder's output gradients (uda.DACS: ImageNet feature distance)
+                img_grad_hook(d_img)
+            self.backbone_image.bwd(sv['image'], d_img)
         if 'isr' in sv and d_isr is not None:
             self.backbone_events.bwd(sv['isr'], as_list(d_isr))
         if 'events' in sv and d_evt is not None:
@@ -281,8 +284,10 @@ class FusionEncoderDecoder(nn.Module):
         feats = [(J, h, w) for J, (h, w) in zip(joint, shapes)]
         return feats, names, (sv_i, sv_e, sv_f, n, G), B
 
-    def _extract_joint_bwd(self, sv, dJ, B, tail_key=None):
-        """dJ: {level: d J_l}; the gradient blocks are consumed in place (fusion contributions are added into blocks 0 and 2)"""
+    def _extract_joint_bwd(self, sv, dJ, B, tail_key=None, img_grad_hook=None):
+        """dJ: {level: d J_l}; the gradient blocks are consumed in place (fusion contributions are added into blocks 0 and 2).
+        img_grad_hook(d_img): called with the image encoder's four output gradients (rows of every pass, pass 0 first) before its
+        backward pass starts -- it may add into them in place"""
         sv_i, sv_e, sv_f, n, G = sv
         d = [dJ.get(i) for i in range(4)]
         d_fus = [(t[m:2 * m] if t is not None else None) for t, m in zip(d, n)]
@@ -303,6 +308,8 @@ class FusionEncoderDecoder(nn.Module):
             d_ev.append(t[2 * m:G * m])
         with rt.lane('enc', *[t for t in d if t is not None]):
             self.backbone_events.bwd(sv_e, d_ev)
+        if img_grad_hook is not None:
+            img_grad_hook(d_img)
         self.backbone_image.bwd(sv_i, d_img)
         if tail_key is not None:   # the decode head's postponed weight gradients: behind the (shorter) image-encoder chain
             ops.run_tail(tail_key)
@@ -325,7 +332,8 @@ class FusionEncoderDecoder(nn.Module):
         the reference's `backward()` calls just add their gradients up.  Per-pass state -- BatchNorm batch statistics and the
         order of the running-statistic updates, the loss normalisation -- is kept per pass (DAFormerHeadFusion.fwd_joint).
         Returns ([(loss, losses)] per pass, saved); `train_bwd(saved, gscale)` back-propagates the SUM of the pass losses.
-        before_head: called between the encoders / fusion blocks and the decode head -- the first use of the targets."""
+        before_head: called between the encoders / fusion blocks and the decode head -- the first use of the targets.
+        saved[5] = the joint feature buffers [(J_l, h, w)] (block 0 of J_l: the image encoder's rows, pass 0's samples first)."""
         first = passes[0][0]
         assert self._joint_ok(first['image'], first['events'], cfg)
         P = len(passes)
@@ -335,9 +343,10 @@ class FusionEncoderDecoder(nn.Module):
             before_head()
         losses, logits, sv_h = self.decode_head.fwd_train_joint(feats, names, Bt // P, [p[1] for p in passes],
                                                                 [p[2] for p in passes], cfg, passes=P)
-        return [(l['loss_seg'], l) for l in losses], ('joint', sv, sv_h, Bt, P)
+        return [(l['loss_seg'], l) for l in losses], ('joint', sv, sv_h, Bt, P, feats)
 
-    def train_bwd(self, saved, gscale):
+    def train_bwd(self, saved, gscale, img_grad_hook=None):
+        """img_grad_hook: see _extract_joint_bwd (the image encoder's output gradients, before its backward pass)"""
         with ops.ln_deferral():   # LayerNorm parameter gradients of the whole pass folded by one launch at the end
             if saved[0] == 'joint':
                 _, sv, sv_h, B = saved[:4]
@@ -356,7 +365,7 @@ class FusionEncoderDecoder(nn.Module):
                 finally:
                     ops.GD_QUEUE_KEY = None
                 if tail:
-                    self._extract_joint_bwd(sv, dJ, B, tail_key='main/headtail')
+                    self._extract_joint_bwd(sv, dJ, B, tail_key='main/headtail', img_grad_hook=img_grad_hook)
                     return
                 if rt.lane_enabled('hw') and rt.grad_ready_hook is None:
                     # the decode head's queued weight gradients (dense 256 x 256-tile GEMMs, ~3.5 ms at 2 + 2 samples) are off the
@@ -366,13 +375,13 @@ class FusionEncoderDecoder(nn.Module):
                 else:
                     ops.gemm_flush_deferred()   # the decode head's queued weight gradients
                 rt.notify_grads_ready('decode_head', self.decode_head)
-                self._extract_joint_bwd(sv, dJ, B)
+                self._extract_joint_bwd(sv, dJ, B, img_grad_hook=img_grad_hook)
                 rt.join_lanes('hw')
                 return
             sv, sv_h, B = saved
             dfeats = self.decode_head.bwd_train(sv_h, B, gscale)
             rt.notify_grads_ready('decode_head', self.decode_head)
-            self._extract_bwd(sv, dfeats, B)
+            self._extract_bwd(sv, dfeats, B, img_grad_hook=img_grad_hook)
             rt.join_lanes('wgrad')
 
     def forward_train(self, inputs, gt_semantic_seg, seg_weight=None, return_feat=False, cfg=None):

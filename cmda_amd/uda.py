@@ -11,8 +11,11 @@ work runs, not what is computed:
   * ClassMix of image / events / label / weight: batched kernels (no per-sample Python loop);
   * ISR of the mixed image: on the device (the reference round-trips every sample through PIL on the host);
   * log values stay device scalars (`_parse_losses`' `.item()` syncs are gone); call `log_vars_to_float` when logging.
-Out of scope here: the other six train types, OrgDACS, ImageNet feature distance, the
-matplotlib debug panels, sky-mask / flare / cow-mask augmentations.
+  * ImageNet feature distance (imnet_feature_dist_lambda > 0, dacs.py:328-354, :566-577): the frozen encoder runs beside the
+    teacher, the label rescale / class mask and the masked distance are two kernels (feat_dist.hip), and the distance's gradient is
+    added into the student image encoder's stage-4 output gradient of the source rows before that encoder's backward pass.
+Out of scope here: the other six train types, OrgDACS, the matplotlib debug panels,
+sky-mask / flare / cow-mask augmentations.
 """
 import os
 import random
@@ -75,7 +78,12 @@ class DACS(nn.Module):
         self.psweight_ignore_top = cfg['pseudo_weight_ignore_top']
         self.psweight_ignore_bottom = cfg['pseudo_weight_ignore_bottom']
         self.fdist_lambda = cfg['imnet_feature_dist_lambda']
-        assert not self.fdist_lambda > 0, 'ImageNet feature distance is off in configs/fusion/* and not implemented'
+        self.fdist_classes = cfg.get('imnet_feature_dist_classes')
+        self.fdist_scale_min_ratio = cfg.get('imnet_feature_dist_scale_min_ratio')
+        self.enable_fdist = self.fdist_lambda > 0
+        if self.enable_fdist and self.fdist_classes is not None:
+            # (downscale_label_ratio compares the cell ratios against it: the reference fails on None here as well)
+            assert self.fdist_scale_min_ratio is not None, 'imnet_feature_dist_classes needs imnet_feature_dist_scale_min_ratio'
         self.mix = cfg['mix']
         assert self.mix == 'class'
         self.blur = cfg['blur']
@@ -97,6 +105,18 @@ class DACS(nn.Module):
             for p in self.cyclegan_itrd2en.parameters():
                 p.requires_grad_(False)
                 p._cmda_frozen = True   # runtime: its re-laid-out compute copies survive optimizer steps
+        self.imnet_model = None
+        if self.enable_fdist:
+            # dacs.py:234-242: an EncoderDecoder over the image backbone's config and the model's decode head (built, never used),
+            # ImageNet weights from init_weights; frozen: no optimizer, no EMA, no gradient exchange sees it
+            m = deepcopy(cfg['model'])
+            self.imnet_model = build_segmentor(dict(type='EncoderDecoder', backbone=m['backbone_image'], decode_head=m['decode_head'],
+                                                    pretrained=m.get('pretrained'), train_cfg=m.get('train_cfg'),
+                                                    test_cfg=m.get('test_cfg')))
+            for p in self.imnet_model.parameters():
+                p.requires_grad_(False)
+                p._cmda_frozen = True   # runtime: its re-laid-out compute copies survive optimizer steps
+        self.debug_fdist_mask = self.debug_gt_rescale = None
         assert cfg.get('sky_mask') is None, 'sky-mask augmentation is off in configs/fusion/* and not implemented'
         self.mixed_image_to_mixed_isr = bool(cfg.get('mixed_image_to_mixed_isr'))
         self.isr_parms = {'val_range': (1, 10 ** 2), '_threshold': 0.04, '_clip_range': 0.2, 'shift_pixel': 3}
@@ -136,9 +156,15 @@ class DACS(nn.Module):
     def simple_test(self, rescale=True, **kwargs):
         return self.get_model().simple_test(rescale, **kwargs)
 
+    def get_imnet_model(self):
+        return self.imnet_model
+
     def init_weights(self):
         self.model.init_weights()
         self.ema_model.init_weights()
+        if self.imnet_model is not None:
+            self.imnet_model.init_weights()   # the model's `pretrained` checkpoint lands here as well
+            rt.refresh_frozen(self.imnet_model)
 
     # -- EMA teacher -----------------------------------------------------------------------------------------------------
     def attach_flat_store(self, opt):
@@ -351,6 +377,35 @@ class DACS(nn.Module):
                 return dict(self.forward_cfg, fusion_isr=True)
         return self.forward_cfg
 
+    # -- ImageNet feature distance (dacs.py:318-354) -------------------------------------------------------------------------------
+    def _fdist_targets(self, day_image, day_label):
+        """the frozen encoder's stage-4 rows over the source image (eval mode: no DropPath; no saved state) and the rescaled label /
+        class mask / device count of downscale_label_ratio (no mask when imnet_feature_dist_classes is None)"""
+        imnet = self.imnet_model
+        if imnet.training:
+            imnet.eval()   # (calc_feat_dist, dacs.py:331)
+        feats, _ = imnet.backbone.fwd(day_image, save=False)
+        ft, h, w = feats[-1]
+        fd = dict(ft=ft, h=h, w=w, rescaled=None, mask=None, count=None)
+        if self.fdist_classes is not None:
+            fd['rescaled'], fd['mask'], fd['count'] = ops.fdist_label_mask(day_label, h, w, self.fdist_classes, self.fdist_scale_min_ratio,
+                                                                           self.num_classes)
+        return fd
+
+    def _fdist_hook(self, fd, student_rows, gscale, log_vars):
+        """img_grad_hook of the student's backward pass: loss and gradient of lambda * masked_feat_dist, the gradient ADDED into the
+        image encoder's stage-4 output gradient of the source rows (the student's source features: `student_rows()`)"""
+        def hook(d_img):
+            n = fd['ft'].shape[0]
+            fs = student_rows()[:n]
+            g = d_img[3]
+            if g is None:
+                g = d_img[3] = torch.zeros(n, fs.shape[1], dtype=fs.dtype, device=fs.device)
+            loss, _ = ops.fdist_fwd_bwd(fs, fd['ft'], self.fdist_lambda, mask=None if fd['mask'] is None else fd['mask'].view(-1),
+                                        count=fd['count'], gscale=gscale, grad=g[:n])
+            log_vars['src.loss_imnet_feat_dist'] = loss.view(())
+        return hook
+
     # -- the device work of one iteration: no host reads, no host-dependent launch shapes (capturable: hipGraph segments) ----------
     def _iteration(self, src, tgt, ctl, use_events, teacher_second, direction):
         """dacs.py:397-860 minus the host decisions (`_draw`), the EMA update and the optimizer step.  `ctl` = device views of
@@ -432,8 +487,12 @@ class DACS(nn.Module):
         if ext_wait is not None:
             rt.wait_external(ext_wait)
         rt.refresh(force=True)   # all re-laid-out weight copies follow this iteration's masters (first node without the overlapped update)
+        fd = None
         if early:
-            with rt.lane('T', night_image, teacher_second, lab, classes, *[v for v in tgt.values() if isinstance(v, torch.Tensor)]):
+            with rt.lane('T', night_image, teacher_second, lab, classes, *[v for v in tgt.values() if isinstance(v, torch.Tensor)],
+                         *((day_image, day_label) if self.enable_fdist else ())):
+                if self.enable_fdist:   # no dependency inside the iteration: ahead of the teacher on its lane (joined before the head)
+                    fd = self._fdist_targets(day_image, day_label)
                 ema, pseudo_label, count, mixed_lbl, mixed_weight = teacher_labels()
             if not pre:
                 mixed_img, mixed_isr = mixed_inputs()
@@ -442,6 +501,8 @@ class DACS(nn.Module):
             with rt.lane('T', night_image, teacher_second, *[v for v in tgt.values() if isinstance(v, torch.Tensor)]):
                 ema, pseudo_label, count, mixed_lbl, mixed_weight = teacher_labels()
                 mixed_img, mixed_isr = mixed_inputs()
+            if self.enable_fdist:   # (this lane: the two-pass route's source backward reads it before lane 'T' is joined)
+                fd = self._fdist_targets(day_image, day_label)
 
         # ---- Image Motion-Extractor (dacs.py:400-404), frozen, no grad ------------------------------------------------------------
         if tt != 'cs2dz_image+raw-isr':
@@ -492,6 +553,8 @@ class DACS(nn.Module):
             ((l_src, d_src), (l_mix, d_mix)), saved = student.train_fwd_passes(
                 [(in_src, day_label, None), (in_mix, mixed_lbl, mixed_weight)], cfg_s,
                 before_head=(lambda: rt.join_lanes('T')) if early else None)
+            # the student's stage-4 image features: block 0 of the joint buffer, the source pass's rows first
+            fd_hook = self._fdist_hook(fd, lambda: saved[5][3][0], one, log_vars) if fd is not None else None
             log_vars['decode.loss_seg'], log_vars['decode.acc_seg'] = l_src, d_src['acc_seg']
             log_vars['mix.decode.loss_seg'], log_vars['mix.decode.acc_seg'] = l_mix, d_mix['acc_seg']
             log_vars['loss'] = l_mix   # _parse_losses of the mixed step overwrites 'loss' (dacs.py:851-857)
@@ -500,21 +563,28 @@ class DACS(nn.Module):
             if hook is not None:
                 rt.grad_ready_hook = hook
             try:
-                student.train_bwd(saved, one)
+                student.train_bwd(saved, one, img_grad_hook=fd_hook)
             finally:
                 rt.grad_ready_hook = prev_hook
             del saved
         else:
             # two passes (routes the joint pass does not cover): the mixed forward runs after the source forward (BatchNorm
             # running statistics), next to the source backward; the mixed backward follows the join (gradients accumulate)
-            loss, (losses, _, _), saved_src = student.train_fwd(in_src, day_label, None, cfg_s)
+            loss, (losses, _, feats_src), saved_src = student.train_fwd(in_src, day_label, None, cfg_s)
             log_vars['decode.loss_seg'], log_vars['decode.acc_seg'], log_vars['loss'] = loss, losses['acc_seg'], loss
             with rt.lane('T'):
                 loss, (losses, _, _), saved_mix = student.train_fwd(in_mix, mixed_lbl, mixed_weight, cfg_s)
             log_vars['mix.decode.loss_seg'], log_vars['mix.decode.acc_seg'] = loss, losses['acc_seg']
             log_vars['loss'] = loss   # _parse_losses of the mixed step overwrites 'loss' (dacs.py:851-857)
-            student.train_bwd(saved_src, one)
-            del saved_src
+            fd_hook = None
+            if fd is not None:
+                if early:   # (the frozen encoder ran on lane 'T', which this route joins only behind the source backward)
+                    rt.join_lanes('T')
+                # the source pass's stage-4 image rows: the joint buffer's block 0, or the image encoder's own output
+                rows4 = (lambda: feats_src[3][0]) if saved_src[0] == 'joint' else (lambda: feats_src['f_image'][3][0])
+                fd_hook = self._fdist_hook(fd, rows4, one, log_vars)
+            student.train_bwd(saved_src, one, img_grad_hook=fd_hook)
+            del saved_src, feats_src
             rt.join_lanes('T')
             if hook is not None:   # the second (last) backward pass: see above
                 rt.grad_ready_hook = hook
@@ -526,6 +596,8 @@ class DACS(nn.Module):
         extras = dict(mixed_img=mixed_img, mixed_lbl=mixed_lbl, mixed_isr=mixed_isr, pseudo_weight=mixed_weight,
                       pseudo_label=pseudo_label, classes=classes, mixed_events=mixed_events, day_events=day_events,
                       teacher_logits=ema, pseudo_count=count)
+        if fd is not None:
+            extras.update(fdist_feat_imnet=fd['ft'], fdist_mask=fd['mask'], fdist_gt_rescale=fd['rescaled'], fdist_count=fd['count'])
         return log_vars, extras
 
     # -- hipGraph replay of the iteration ------------------------------------------------------------------------------------------
@@ -648,4 +720,8 @@ class DACS(nn.Module):
             log_vars, extras = self._iteration(src, tgt, cb['d'], struct_events, second, ndir_key)
         self.local_iter += 1
         self.last_mix = extras
+        if extras.get('fdist_mask') is not None:   # calc_feat_dist's debug tensors (dacs.py:346-347), [B, 1, h, w] as there
+            B_, h_, w_ = extras['fdist_mask'].shape
+            self.debug_fdist_mask = extras['fdist_mask'].view(torch.bool).view(B_, 1, h_, w_)
+            self.debug_gt_rescale = extras['fdist_gt_rescale'].view(B_, 1, h_, w_)
         return dict(log_vars)

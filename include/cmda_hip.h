@@ -256,6 +256,22 @@ int cmda_pseudo_weight(const int* count, float* weight, int B, int H, int W, int
 int cmda_upsample_logits_nchw(const float* logits, float* out, int B, int h, int w, int H, int W, int nc, void*
     stream);
 
+/* ---- ImageNet feature distance (uda/dacs.py:318-354 masked_feat_dist / calc_feat_dist; utils/utils.py:18-39
+ * downscale_label_ratio).  Additive entry points of ABI 8; both launches are deterministic (integer counters, fixed-order sums).
+ * cmda_fdist_label_mask: label int64 [B][H][W], H = h*s and W = w*s (else CMDA_ERR_SHAPE) -> rescaled int64 [B][h][w] (first-max
+ *   class of each s x s cell, the ignore index counted as class nc; ignore_index where that class wins or count/(s*s) < min_ratio),
+ *   mask uint8 [B][h][w] = rescaled in class_bits (bit c = class c), row_counts int32 [B*h] (masked cells per cell row) and
+ *   count int32 [1] (masked cells).  ticket: int32 [1], zero before the call and left zero.
+ * cmda_fdist_fwd_bwd: fs / ft = student / frozen-encoder rows [rows][C] (dtype; C a multiple of 16 bytes' elements), mask uint8
+ *   [rows] or NULL (every row), count int32 [1] on the device (NULL: rows) -> norms fp32 [rows] (||fs - ft||_2, 0 off the mask),
+ *   loss fp32 [1] = lambda * mean of the masked norms (NaN for count = 0) and, when grad != NULL, grad[r*ldg + c] (grad_dtype:
+ *   dtype, or CMDA_F32 under bf16 rows) +=
+ *   gscale[0] * lambda / count * (fs - ft) / ||fs - ft|| on masked rows of non-zero norm (gscale NULL = 1).  ticket as above. */
+int cmda_fdist_label_mask(const int64_t* label, int B, int H, int W, int h, int w, int nc, int ignore_index, float min_ratio,
+    uint32_t class_bits, int64_t* rescaled, uint8_t* mask, int* row_counts, int* count, int* ticket, void* stream);
+int cmda_fdist_fwd_bwd(const void* fs, const void* ft, const uint8_t* mask, const int* count, int rows, int C, int64_t ldg,
+    float lambda, const float* gscale, void* grad, float* norms, float* loss, int* ticket, int dtype, int grad_dtype, void* stream);
+
 /* ---- Data movement / pointwise -- permute+cast (NLC<->NCHW boundary copies mix_transformer.py:406-430 and conv-weight
  * repacks), bias gradient, a*x+b*y (fusion/attention_avg_fusion.py:49), DropPath / Dropout2d scaling (timm DropPath
  * mix_transformer.py:134,145-146; nn.Dropout2d decode_head.py:565-566), strided 2-D copy (torch.cat fusion/attention_fusion.py:52). */
