@@ -5,10 +5,17 @@ DACS uses it (uda/dacs.py:96-103,400-404: define_G() = 1->1 channels, ngf 64, In
 padding, 9 blocks, run frozen under no_grad on mean_c(img_time_res)).  Parameter names are the reference's
 `model.<idx>...` so `cityscapes_ICD_to_dsec_EN.pth` loads with load_state_dict.
 
+The 3 -> 3 form (define_G(input_nc=3, output_nc=3): the day -> night generator of the image-only type 'cs2dz_image',
+dacs.py:105-113,368-372) runs the same way; `set_io_affine` folds the input re-normalisation into the first convolution's weights
+(reflection padding commutes with a per-channel affine map) and the output's into the epilogue of the last layer's stencil kernel
+(conv_co1.hip, cmda_conv_co3), so neither costs a pass of its own.
+
 Every convolution is an implicit GEMM on the MFMA kernel (reflection padding and the transposed convolutions'
 zero insertion are address modes of the operand view, gemm.hip view_offset); InstanceNorm reuses the column-statistics
 kernels of batchnorm.hip per sample.
 """
+import types
+
 import torch
 import torch.nn as nn
 
@@ -44,6 +51,39 @@ class ResnetGenerator(nn.Module):
         self.model = nn.Sequential(*m)
         self.n_blocks = n_blocks
         self._ident = {}
+        self._in_affine = self._out_affine = None
+        self._fold = None
+
+    def set_io_affine(self, in_scale=None, in_shift=None, out_scale=None, out_shift=None):
+        """G(x * in_scale + in_shift) * out_scale + out_shift per channel (tanh before the output map), without extra passes: the input
+        map folded into the first convolution, the output map in the last layer's epilogue.  None = identity."""
+        vec = lambda v: None if v is None else torch.as_tensor(v, dtype=torch.float32).flatten()  # noqa: E731
+        self._in_affine = None if in_scale is None else (vec(in_scale), vec(in_shift))
+        self._out_affine = None if out_scale is None else (vec(out_scale), vec(out_shift))
+        self._fold = None
+
+    def _first_conv(self):
+        """the first convolution's (weight, bias) with the input map folded in: conv(a x + b) = conv_{W a}(x) + sum_{ci,kh,kw} W b
+        (exact under reflection padding).  Recomputed when the weights change (load_state_dict bumps their version)."""
+        conv = self.model[1]
+        if self._in_affine is None:
+            return conv.weight, conv.bias
+        key = (conv.weight._version, conv.bias._version, conv.weight.data_ptr(), str(conv.weight.device))
+        if self._fold is None or self._fold[0] != key:
+            a, b = (t.to(conv.weight.device) for t in self._in_affine)
+            w = conv.weight.detach()
+            wf = nn.Parameter(w * a.view(1, -1, 1, 1), requires_grad=False)
+            wf._cmda_frozen = True   # runtime: a frozen compute copy, as the generator's own weights
+            bf = conv.bias.detach() + (w * b.view(1, -1, 1, 1)).sum(dim=(1, 2, 3))
+            self._fold = (key, wf, bf)
+        return self._fold[1], self._fold[2]
+
+    def _out_map(self, dev):
+        if self._out_affine is None:
+            return None, None
+        if getattr(self, '_out_dev', None) is None or self._out_dev[0].device != dev:
+            self._out_dev = tuple(t.to(dev) for t in self._out_affine)
+        return self._out_dev
 
     def _inorm(self, x, B, HW, C, relu, res=None, out_dtype=None, copy=False, stats=None):
         """InstanceNorm2d(affine=False, eps 1e-5) (+ReLU) (+ fp32 residual) on NHWC-flat x [B*HW, C]: the grouped column-statistics
@@ -101,10 +141,13 @@ class ResnetGenerator(nn.Module):
 
     @ops.sited('generator')
     @torch.no_grad()
-    def forward(self, inp):
-        """inp fp32 NCHW [B,1,H,W] -> fp32 NCHW [B,1,H,W] (tanh)."""
+    def forward(self, inp, last_route='auto'):
+        """inp fp32 NCHW [B,Ci,H,W] -> fp32 NCHW [B,Co,H,W] (tanh, then the output map of set_io_affine).
+        last_route: 'auto' (the stencil kernel where it takes the shape), or 'gemm' (the implicit-GEMM form of the last layer: timing)"""
         B, Cin, H, W = inp.shape
         m = self.model
+        w1, b1 = self._first_conv()
+        first = types.SimpleNamespace(weight=w1, bias=b1, out_channels=m[1].out_channels)
         cp = rt.conv_channel_pad(Cin)   # bf16 mode: the 1-channel input padded to 8 (16-byte im2col chunks: the LDS-DMA GEMM path)
         x = torch.empty(B * H * W, cp, dtype=rt.compute_dtype(), device=inp.device)
         if cp != Cin:
@@ -112,11 +155,11 @@ class ResnetGenerator(nn.Module):
             H1, W1 = K.conv_out_size(H + 6, W + 6, 7, 1, 0)
             c = torch.empty(B * H1 * W1, m[1].out_channels, dtype=torch.float32, device=inp.device)
             ws = self._stats_ws(inp.device, B, H1 * W1, m[1].out_channels)
-            K.conv_fwd(x, m[1].weight, m[1].bias, B, H, W, 1, 3, 1, reflect=1, ci_pad=cp, out=c,
+            K.conv_fwd(x, first.weight, first.bias, B, H, W, 1, 3, 1, reflect=1, ci_pad=cp, out=c,
                        colstats=None if ws is None else (ws, H1 * W1))
         else:
             ops.permute4(inp.contiguous(), x, (B, Cin, H, W), (0, 2, 3, 1))
-            c, H1, W1, ws = self._conv(x, m[1], B, H, W, 1, 3, 1, stats=True)
+            c, H1, W1, ws = self._conv(x, first, B, H, W, 1, 3, 1, stats=True)
         # every InstanceNorm below takes its statistics from the epilogue of the convolution in front of it (`ws`)
         x = self._inorm(c, B, H1 * W1, m[1].out_channels, True, stats=ws)
         c, H2, W2, ws = self._conv(x, m[4], B, H1, W1, 2, 1, 0, stats=True)
@@ -140,9 +183,15 @@ class ResnetGenerator(nn.Module):
         last = m[k + 7]
         Co = last.out_channels
         Ci = last.in_channels
-        if Co == 1 and ops.conv_co1_ok(x, Ci, 7, 3):   # one output channel: a stencil kernel, not an N = 1 GEMM
+        scale, shift = self._out_map(inp.device)
+        stencil = last_route == 'auto' and ops.conv_co1_ok(x, Ci, 7, 3)
+        if stencil and Co == 1 and scale is None:   # one output channel: a stencil kernel, not an N = 1 GEMM
             y = ops.conv_co1(x, rt.wconv(last.weight), last.bias, B, H5, W5, Ci, 7, 3, True, 'tanh')
             return y.view(B, 1, H5, W5)
+        if stencil and Co == 3:   # three (the 3 -> 3 generator): the same stencil, the output map in its epilogue, NCHW out
+            return ops.conv_co3(x, rt.wconv(last.weight), last.bias, B, H5, W5, Ci, 7, 3, True, 'tanh', scale, shift)
+        if scale is not None:
+            raise NotImplementedError(f'generator output map: only the stencil kernel applies it (Co = {Co}, Ci = {Ci}, route {last_route})')
         y = torch.empty(B * H5 * W5, Co, dtype=torch.float32, device=inp.device)
         ops.gemm(conv_view(x, B, H5, W5, Ci, 7, 7, 1, 3, 1, OH=H5, OW=W5, reflect=1),
                  plain_view(rt.wconv(last.weight), Co, 49 * Ci), y, B * H5 * W5, Co, 49 * Ci, dtype=rt.tag(),

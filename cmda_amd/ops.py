@@ -618,6 +618,18 @@ def conv_co1(x, w, bias, B, H, W, C, K, pad, reflect, act):
     return out
 
 
+def conv_co3(x, w, bias, B, H, W, C, K, pad, reflect, act, scale=None, shift=None):
+    """x [B*H*W, C] NHWC, w [3, K*K*C] khwc (activation dtype) -> fp32 NCHW [B,3,H,W] = act(bias + conv) * scale + shift (per output
+    channel; scale / shift fp32 [3] or both None): three output channels (conv_co1_ok decides the shapes)"""
+    check_dev(x, w, bias, scale, shift)
+    if (scale is None) != (shift is None):
+        raise L.CmdaError('conv_co3: scale and shift go together')
+    out = torch.empty(B, 3, H, W, dtype=torch.float32, device=x.device)
+    call('cmda_conv_co3', ptr(x), ptr(w), ptr(bias), ptr(scale), ptr(shift), ptr(out), c_i32(B), c_i32(H), c_i32(W), c_i32(C), c_i32(K),
+         c_i32(pad), c_i32(int(reflect)), c_i32(ACT[act]), dtype_tag(x), stream_of(x))
+    return out
+
+
 def cast_pad_cols(src32, cp, dtype):
     """fp32 [rows, c] -> dtype [rows, cp], columns >= c zero"""
     check_dev(src32)

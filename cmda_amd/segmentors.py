@@ -1,4 +1,4 @@
-"""Segmentors on the HIP kernels -- registry keys `EncoderDecoder`, `FusionEncoderDecoder`.
+"""Segmentors on the HIP kernels -- registry keys `EncoderDecoder`, `EventsEncoderDecoder`, `FusionEncoderDecoder`.
 
 Mirrors mmseg/models/segmentors/encoder_decoder.py (EncoderDecoder :19-300; FusionEncoderDecoder :625-1003:
 extract_feat :698-721, encode_decode :723-746, forward_train :794-831) and base.py `_parse_losses` :710-743.
@@ -119,6 +119,114 @@ class EncoderDecoder(nn.Module):
         if meta.get('flip'):
             seg_logit = seg_logit.flip(dims=(3,) if meta['flip_direction'] == 'horizontal' else (2,))
         return list(seg_logit.argmax(dim=1).cpu().numpy())
+
+
+@SEGMENTORS.register_module()
+class EventsEncoderDecoder(EncoderDecoder):
+    """encoder_decoder.py:308-620 for the image-only train types 'cs2dsec_image' / 'cs2dz_image' (DAFormer's DACS baseline): one
+    MiT on the 3-channel image, a plain DAFormerHead.  The reference also accepts events (concatenated to the image, or alone,
+    :365-374); those forms are out of scope here and raise.  State-dict keys: `backbone.*`, `decode_head.*`, as the reference's."""
+
+    def __init__(self, backbone, decode_head, neck=None, auxiliary_head=None, train_cfg=None, test_cfg=None, pretrained=None,
+                 init_cfg=None, **kwargs):
+        in_chans = backbone.get('in_chans', 3)
+        if in_chans != 3:
+            raise ValueError(f'EventsEncoderDecoder: in_chans={in_chans}; only the image-only form (in_chans=3, events=None) is '
+                             'implemented -- the concatenated image+events and the events-only inputs are not')
+        super().__init__(backbone, decode_head, neck, auxiliary_head, train_cfg, test_cfg, pretrained, init_cfg)
+
+    @staticmethod
+    def _image_only(image, events):
+        if events is not None:
+            raise NotImplementedError('EventsEncoderDecoder: event inputs (image+events concatenated, or events alone) are not '
+                                      'implemented; pass events=None')
+        if image is None:
+            raise ValueError('EventsEncoderDecoder: an image is required')
+        return image
+
+    def extract_feat(self, image, events=None):
+        return self.backbone(self._image_only(image, events))
+
+    # hand-scheduled training pass (the same as EncoderDecoder's, plus the stage outputs and the image-gradient hook uda.DACS needs)
+    def train_fwd(self, img, gt, seg_weight):
+        """returns (loss, (losses, logits, feats), saved); feats = the backbone's [(rows [B*N, C], h, w)] * 4"""
+        B = img.shape[0]
+        feats, sv_b = self.backbone.fwd(img)
+        losses, logits, sv_h = self.decode_head.fwd_train(feats, B, gt, seg_weight)
+        return losses['loss_seg'], (losses, logits, feats), (sv_b, sv_h, B)
+
+    def train_bwd(self, saved, gscale, img_grad_hook=None):
+        """img_grad_hook(d): called with the backbone's four output gradients before its backward pass starts; it may add into
+        them in place, or fill a None entry (uda.DACS: the ImageNet feature distance on stage 4)"""
+        sv_b, sv_h, B = saved
+        with ops.ln_deferral():
+            dfs = self.decode_head.bwd_train(sv_h, B, gscale)
+            if rt.grad_ready_hook is not None:
+                ops.gemm_flush_deferred()   # the head's queued weight gradients are final before they are reported
+            rt.notify_grads_ready('decode_head', self.decode_head)
+            d = [dfs.get(i) for i in range(4)]
+            if img_grad_hook is not None:
+                img_grad_hook(d)
+            self.backbone.bwd(sv_b, d)
+        rt.join_lanes('wgrad')
+
+    def forward_train(self, image, events, gt_semantic_seg, seg_weight=None, return_feat=False):
+        """encoder_decoder.py:446-482: (losses, seg_logits) -- seg_logits NCHW fp32 at 1/4 resolution"""
+        img = self._image_only(image, events)
+        holder = {}
+        loss = _TrainFn.apply(_Capture(self, holder), rt.anchor(img.device), (img, gt_semantic_seg, seg_weight))
+        losses, logits, feats = holder['aux']
+        out = {}
+        if return_feat:
+            out['features'] = feats
+        out.update(add_prefix({'loss_seg': loss, 'acc_seg': losses['acc_seg']}, 'decode'))
+        return out, logits.permute(0, 3, 1, 2)
+
+    # -- inference / teacher ---------------------------------------------------------------------------------------------
+    def encode_decode_lowres(self, img, events=None, test_cfg=None):
+        """fp32 NHWC logits [B, H/4, W/4, nc] (the teacher: the fused pseudo-label kernel up-samples on the fly)"""
+        img = self._image_only(img, events)
+        with torch.no_grad():
+            feats, _ = self.backbone.fwd(img, save=False)
+            logits, _ = self.decode_head.fwd(feats, img.shape[0])
+        return logits
+
+    def encode_decode(self, img, events=None):
+        """:376-387: logits NCHW at the input size"""
+        H, W = img.shape[2:]
+        return ops.upsample_logits_nchw(self.encode_decode_lowres(img, events), H, W)
+
+    def whole_inference(self, rescale, **kwargs):
+        """:525-551: the input keyed by `image`, else `warp_image`; resized to img_metas['ori_shape'] when `rescale`"""
+        img = kwargs['image'] if 'image' in kwargs else kwargs.get('warp_image')
+        if isinstance(img, list):
+            img = img[0]
+        events = None if 'image' in kwargs else kwargs.get('events_vg')
+        seg_logit = self.encode_decode(img, events)
+        meta = kwargs.get('img_metas')
+        if rescale and meta is not None:
+            meta = meta[0] if isinstance(meta, (list, tuple)) else meta
+            size = tuple(meta['ori_shape'][:2])
+            if size != tuple(seg_logit.shape[2:]):
+                seg_logit = ops.upsample_logits_nchw(seg_logit.permute(0, 2, 3, 1).contiguous(), size[0], size[1])
+        return seg_logit
+
+    def inference(self, rescale, **kwargs):
+        """:553-588 (test_cfg.mode 'whole'): soft-max of the logits, flipped back when the test pipeline flipped"""
+        mode = (self.test_cfg or {}).get('mode', 'whole')
+        if mode != 'whole':
+            raise NotImplementedError(f"EventsEncoderDecoder: test_cfg.mode '{mode}' (only 'whole' is implemented)")
+        output = torch.softmax(self.whole_inference(rescale, **kwargs), dim=1)
+        meta = kwargs.get('img_metas')
+        meta = (meta[0] if isinstance(meta, (list, tuple)) else meta) or {}
+        if meta.get('flip'):
+            assert meta['flip_direction'] in ('horizontal', 'vertical')
+            output = output.flip(dims=(3,) if meta['flip_direction'] == 'horizontal' else (2,))
+        return output
+
+    def simple_test(self, rescale=True, **kwargs):
+        """:590-603: per-image label maps (numpy)"""
+        return list(self.inference(rescale, **kwargs).argmax(dim=1).cpu().numpy())
 
 
 class _Capture:

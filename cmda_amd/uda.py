@@ -14,8 +14,11 @@ work runs, not what is computed:
   * ImageNet feature distance (imnet_feature_dist_lambda > 0, dacs.py:328-354, :566-577): the frozen encoder runs beside the
     teacher, the label rescale / class mask and the masked distance are two kernels (feat_dist.hip), and the distance's gradient is
     added into the student image encoder's stage-4 output gradient of the source rows before that encoder's backward pass.
-Out of scope here: the other six train types, OrgDACS, the matplotlib debug panels,
-sky-mask / flare / cow-mask augmentations.
+The image-only train types 'cs2dsec_image' / 'cs2dz_image' (DAFormer's DACS on one MiT and a plain DAFormerHead, the baseline the
+fusion types are compared against; dacs.py:363-377 and the image branches below) run through `_iteration_image`: no events, no ISR,
+no fusion; for 'cs2dz_image' optionally the frozen 3 -> 3 day -> night generator on the source image (cyclegan_id2in_path).
+Out of scope here: the remaining train types ('cs2dz_image+d2n-isr', '_split', '_no-fusion'), OrgDACS,
+LightNet (cyclegan_light_path), the matplotlib debug panels, sky-mask / flare / cow-mask augmentations.
 """
 import os
 import random
@@ -63,7 +66,10 @@ GRAPH_LANES = tuple(x for x in os.environ.get('CMDA_GRAPH_LANES', 'enc,T,Tenc,wq
 
 @UDA.register_module()
 class DACS(nn.Module):
-    SUPPORTED = {'cs2dsec_image+events', 'cs2dz_image+raw-isr', 'cs2dsec_image+events_together'}
+    SUPPORTED = {'cs2dsec_image+events', 'cs2dz_image+raw-isr', 'cs2dsec_image+events_together', 'cs2dsec_image', 'cs2dz_image'}
+    IMAGE_TYPES = {'cs2dsec_image', 'cs2dz_image'}   # image-only: EventsEncoderDecoder, no events / ISR / fusion (_iteration_image)
+    # ImageNet mean / std of the image normalisation (get_mean_std): the day -> night generator works on [-1, 1] images
+    IMNET_MEAN, IMNET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
     def __init__(self, **cfg):
         super().__init__()
@@ -93,6 +99,7 @@ class DACS(nn.Module):
         self.ema_model = build_segmentor(deepcopy(cfg['model']))
         self.train_type = cfg['train_type']
         assert self.train_type in self.SUPPORTED, f'train_type {self.train_type} is outside the accelerated hot path'
+        self.image_only = self.train_type in self.IMAGE_TYPES
         self.forward_cfg = dict(cfg['forward_cfg'])
         self.img_self_res_reg = cfg.get('img_self_res_reg', 'no')
         path = cfg.get('cyclegan_itrd2en_path', '')
@@ -105,8 +112,33 @@ class DACS(nn.Module):
             for p in self.cyclegan_itrd2en.parameters():
                 p.requires_grad_(False)
                 p._cmda_frozen = True   # runtime: its re-laid-out compute copies survive optimizer steps
+        self.cyclegan_id2in = None
+        path = cfg.get('cyclegan_id2in_path', '')
+        if path and self.train_type == 'cs2dz_image':
+            # dacs.py:105-113, :368-372: the source image through a frozen 3 -> 3 generator, [-1, 1] in and out:
+            # G((x * std + mean - 0.5) / 0.5) / 2 + 0.5 - mean) / std -- both maps folded into the generator's first / last layer
+            self.cyclegan_id2in = define_G(input_nc=3, output_nc=3)
+            if path != 'random':  # 'random' = seeded random init (no checkpoint exists offline; bench / tests)
+                self.cyclegan_id2in.load_state_dict(torch.load(path, map_location='cpu'))
+            mean, std = torch.tensor(self.IMNET_MEAN), torch.tensor(self.IMNET_STD)
+            self.cyclegan_id2in.set_io_affine(2.0 * std, 2.0 * (mean - 0.5), 0.5 / std, (0.5 - mean) / std)
+            self.cyclegan_id2in.eval()
+            for p in self.cyclegan_id2in.parameters():
+                p.requires_grad_(False)
+                p._cmda_frozen = True
+        if cfg.get('cyclegan_light_path', '') and self.train_type == 'cs2dz_image':
+            # (dacs.py:115-123 loads a LightNet whose use is commented out, :373-377 and encoder_decoder.py:364-367)
+            raise ValueError("cyclegan_light_path: LightNet is not implemented (the reference loads it but never applies it); "
+                             "leave cyclegan_light_path empty")
         self.imnet_model = None
-        if self.enable_fdist:
+        if self.enable_fdist and self.image_only:
+            # dacs.py:234-241: for the image-only types a copy of the model config itself -- an EventsEncoderDecoder whose decode head is
+            # built and never used; frozen as below
+            self.imnet_model = build_segmentor(deepcopy(cfg['model']))
+            for p in self.imnet_model.parameters():
+                p.requires_grad_(False)
+                p._cmda_frozen = True
+        elif self.enable_fdist:
             # dacs.py:234-242: an EncoderDecoder over the image backbone's config and the model's decode head (built, never used),
             # ImageNet weights from init_weights; frozen: no optimizer, no EMA, no gradient exchange sees it
             m = deepcopy(cfg['model'])
@@ -122,7 +154,8 @@ class DACS(nn.Module):
         self.isr_parms = {'val_range': (1, 10 ** 2), '_threshold': 0.04, '_clip_range': 0.2, 'shift_pixel': 3}
         if cfg.get('isr_parms'):
             self.isr_parms = dict(cfg['isr_parms'])
-        assert self.mixed_image_to_mixed_isr, 'configs/fusion/* recompute the ISR from the mixed image'
+        # (the reference recomputes the ISR of the mixed image for its ISR types only, dacs.py:727; the image-only types have none)
+        assert self.image_only or self.mixed_image_to_mixed_isr, 'configs/fusion/* recompute the ISR from the mixed image'
         self.isr_another_fusion = bool(cfg.get('isr_another_fusion'))
         self.fuse_both_ice_and_e = bool(cfg.get('fuse_both_ice_and_e'))
         self.without_events = bool(cfg.get('without_events'))
@@ -284,7 +317,9 @@ class DACS(nn.Module):
         per-sample kornia ColorJitter draws of strong_transform (one call per sample, dacs.py:721-724)."""
         B = day_label.shape[0]
         d = {}
-        if self.train_type == 'cs2dz_image+raw-isr':
+        if self.image_only:
+            d['choice'] = None   # (no events / ISR choice: the torch.rand of dacs.py:414-417 is in the events branch only)
+        elif self.train_type == 'cs2dz_image+raw-isr':
             d['choice'] = 0.0
         elif self.without_events:
             d['choice'] = -1.0
@@ -411,6 +446,8 @@ class DACS(nn.Module):
         """dacs.py:397-860 minus the host decisions (`_draw`), the EMA update and the optimizer step.  `ctl` = device views of
         the control block; `teacher_second` = the teacher's second input (events or ISR, already chosen); `use_events` /
         `direction` only select code paths that are fixed per configuration (student inputs of 'cs2dsec_image+events')."""
+        if self.image_only:
+            return self._iteration_image(src, tgt, ctl)
         tt = self.train_type
         opt = getattr(self, '_opt', None)
         ext_wait = (lambda: getattr(opt, '_update_stream', None)) if (opt is not None and getattr(opt, 'overlap', False)) else None
@@ -600,6 +637,80 @@ class DACS(nn.Module):
             extras.update(fdist_feat_imnet=fd['ft'], fdist_mask=fd['mask'], fdist_gt_rescale=fd['rescaled'], fdist_count=fd['count'])
         return log_vars, extras
 
+    def _iteration_image(self, src, tgt, ctl):
+        """the image-only iteration ('cs2dsec_image' / 'cs2dz_image'; dacs.py:363-377, :467-468, :569-570, :597-600, :701-791): the
+        same host / device split and the same step boundary as `_iteration`.  Schedule: the frozen generator (cs2dz_image) first -- it
+        reads no trainable weight, so it runs underneath an overlapped optimizer update; then the teacher, its pseudo-labels / weights
+        and the feature-distance targets on lane 'T' beside the mixed image on this lane; the student's source pass here, its mixed
+        pass on lane 'T' beside the source backward (BatchNorm running statistics: source first, as in the reference); the mixed
+        backward after the join (the gradients add up)."""
+        opt = getattr(self, '_opt', None)
+        ext_wait = (lambda: getattr(opt, '_update_stream', None)) if (opt is not None and getattr(opt, 'overlap', False)) else None
+        day_image, day_label = src['image'], src['label']
+        night_image = tgt['warp_image'] if 'warp_image' in tgt else tgt['image']
+        B, _, H, W = day_image.shape
+        dev = day_image.device
+        log_vars = {}
+        if not self.ema_model.training or not getattr(self, '_teacher_mode_set', False):
+            self.ema_model.train()          # BatchNorm keeps batch statistics (and updates its running stats) ...
+            set_stochastic(self.ema_model, False)  # ... but DropPath / Dropout2d are off in the teacher (dacs.py:458-462)
+            self._teacher_mode_set = True
+        student, teacher = self.get_model(), self.get_ema_model()
+        one = rt.ones1(dev)
+        lab = day_label.view(B, H, W)
+        classes = ctl['classes']
+        if self.cyclegan_id2in is not None:
+            # dacs.py:368-372: the translated image replaces the source image for the source step, the feature distance and the mixing
+            day_image = self.cyclegan_id2in(day_image)
+        if ext_wait is not None:
+            rt.wait_external(ext_wait)
+        rt.refresh(force=True)   # all re-laid-out weight copies follow this iteration's masters
+        fd = None
+        with rt.lane('T', night_image, day_image, day_label, lab, classes):
+            if self.enable_fdist:
+                fd = self._fdist_targets(day_image, day_label)
+            ema = teacher.encode_decode_lowres(night_image)
+            pseudo_label, _, count = ops.pseudo_label(ema, H, W, self.pseudo_threshold, want_prob=False)
+            pseudo_weight = ops.pseudo_weight(count, B, H, W, self.psweight_ignore_top, self.psweight_ignore_bottom)
+            gt_pixel_weight = torch.ones(B, H, W, dtype=torch.float32, device=dev)
+            mixed_lbl = ops.class_mix_label(lab, pseudo_label, lab, classes).view(B, 1, H, W)
+            mixed_weight = ops.class_mix(gt_pixel_weight.view(B, 1, H, W), pseudo_weight.view(B, 1, H, W), lab, classes).view(B, H, W)
+        # ClassMix + strong augmentation of the mixed image (dacs.py:719-724): gates and parameters from the control block
+        mixed_img = ops.class_mix(day_image, night_image, lab, classes)
+        if self.color_jitter_p < 1.0:
+            ops.color_jitter_(mixed_img, ctl['jitter'], ctl['jitter_on'])
+        if self.blur:
+            ops.gaussian_blur_(mixed_img, ctl['taps_x'], ctl['taps_y'], ctl['blur_on'])
+        hook = getattr(self, 'final_pass_grad_hook', None)
+        if hook is not None and dev.type == 'cuda' and torch.cuda.is_current_stream_capturing() and rt._conc['seg'] is None:
+            hook = None   # one monolithic capture cannot call out; the segmented capture records the hook as a host step
+        prev_hook = rt.grad_ready_hook
+        loss, (losses, _, feats_src), saved_src = student.train_fwd(day_image, day_label, None)
+        log_vars['decode.loss_seg'], log_vars['decode.acc_seg'] = loss, losses['acc_seg']
+        with rt.lane('T', mixed_img):
+            loss, (losses, _, _), saved_mix = student.train_fwd(mixed_img, mixed_lbl, mixed_weight)
+        log_vars['mix.decode.loss_seg'], log_vars['mix.decode.acc_seg'] = loss, losses['acc_seg']
+        log_vars['loss'] = loss   # _parse_losses of the mixed step overwrites 'loss' (dacs.py:851-857)
+        fd_hook = None
+        if fd is not None:
+            rt.join_lanes('T')   # (the frozen encoder ran on lane 'T')
+            fd_hook = self._fdist_hook(fd, lambda: feats_src[3][0], one, log_vars)
+        student.train_bwd(saved_src, one, img_grad_hook=fd_hook)
+        del saved_src, feats_src
+        rt.join_lanes('T')
+        if hook is not None:   # the last backward pass: its gradients are final for the step (runtime.grad_ready_hook)
+            rt.grad_ready_hook = hook
+        try:
+            student.train_bwd(saved_mix, one)
+        finally:
+            rt.grad_ready_hook = prev_hook
+        del saved_mix
+        extras = dict(mixed_img=mixed_img, mixed_lbl=mixed_lbl, pseudo_weight=mixed_weight, pseudo_label=pseudo_label, classes=classes,
+                      teacher_logits=ema, pseudo_count=count, day_image=day_image)
+        if fd is not None:
+            extras.update(fdist_feat_imnet=fd['ft'], fdist_mask=fd['mask'], fdist_gt_rescale=fd['rescaled'], fdist_count=fd['count'])
+        return log_vars, extras
+
     # -- hipGraph replay of the iteration ------------------------------------------------------------------------------------------
     def enable_graph(self, warmup_iters=2):
         """Capture `_iteration` after `warmup_iters` eager iterations -- as a chain of linear hipGraph segments replayed on the
@@ -666,8 +777,9 @@ class DACS(nn.Module):
         dev = src['image'].device
         draws = getattr(self, 'inject_draws', None) or self._draw(day_label, H, W)
         self.last_draws = draws
-        self.forward_cfg['isr_events_fusion_choice'] = draws['choice']
-        use_events = tt != 'cs2dz_image+raw-isr' and draws['choice'] > self.random_choice_thres
+        if not self.image_only:
+            self.forward_cfg['isr_events_fusion_choice'] = draws['choice']
+        use_events = not self.image_only and tt != 'cs2dz_image+raw-isr' and draws['choice'] > self.random_choice_thres
         cb = self._control_block(dev, B, H, W)
         self._stage(cb, draws)
         opt = getattr(self, '_opt', None)
@@ -682,7 +794,9 @@ class DACS(nn.Module):
                     self._init_ema_weights()
                 if self.local_iter > 0:
                     self._update_ema(self.local_iter)
-        if tt == 'cs2dz_image+raw-isr':
+        if self.image_only:
+            second = None
+        elif tt == 'cs2dz_image+raw-isr':
             second = tgt['warp_img_self_res'] if 'warp_image' in tgt else tgt['night_isr']
         else:
             second = tgt['events_vg'] if (use_events or self.isr_no_fusion) else tgt['warp_img_self_res']
@@ -709,7 +823,8 @@ class DACS(nn.Module):
             for k, v in G['tgt'].items():
                 if v.data_ptr() != tgt[k].data_ptr():
                     v.copy_(tgt[k])
-            G['second'].copy_(second)
+            if second is not None:
+                G['second'].copy_(second)
             boundary()
             G['graph'].replay()
             log_vars, extras = G['out']

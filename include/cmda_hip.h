@@ -116,6 +116,13 @@ int cmda_gemm(const cmda_gemm_params_t* p, void* stream);
  * dot products) and fp32 storage (both parity modes); CMDA_ERR_UNSUPPORTED otherwise (the caller then uses cmda_gemm). */
 int cmda_conv_co1(const void* x, const void* w, const float* bias, float* out, int B, int H, int W, int C, int K, int pad,
     int reflect, int act, int dtype, void* stream);
+/* The same stencil with THREE output channels (additive entry point of ABI 8): the last layer of the 3 -> 3 day -> night generator of
+ * the image-only DACS type 'cs2dz_image' (ReflectionPad2d(3) + Conv2d(64,3,7) + Tanh, uda/dacs.py:105-113,368-372).  w khwc [3][K*K*C],
+ * bias fp32 [3]; out fp32 NCHW [B,3,H,W] = act(bias[co] + sum) * scale[co] + shift[co] (scale / shift both NULL: no affine, or both
+ * fp32 [3]: the generator output's de-normalisation, (y / 2 + 0.5 - mean) / std).  Same shapes and dtypes as cmda_conv_co1;
+ * CMDA_ERR_UNSUPPORTED otherwise or when only one of scale / shift is given. */
+int cmda_conv_co3(const void* x, const void* w, const float* bias, const float* scale, const float* shift, float* out, int B, int H,
+    int W, int C, int K, int pad, int reflect, int act, int dtype, void* stream);
 
 /* GROUPED launch of n GEMMs that are independent of each other (no problem reads another's output, and outputs shared between
  * problems are ACCUMULATED -- atomic != 0 -- so any order is correct: the grouped buckets are launched first, the problems that
