@@ -12,8 +12,11 @@ accumulate, random-init weights of the real architecture, synthetic inputs shape
 companions).  N>1: one process per GPU (torchrun), weak scaling (2+2 per GPU), gradients averaged with RCCL.
 `--workload supervised` = configs[1] (MiT-B5 + DAFormer head fwd/bwd), kept as a secondary line.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel family = the MFMA GEMM / implicit-GEMM, HIP-event timed
-on the launch stream) and, at N=1, `cpu_baseline` (the oracle restatement timed on the host cores, bounded sample).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the headline
+figure, nothing else.  `--full` adds what takes runs of its own: `roofline` (one more eager step; dominant kernel family = the
+MFMA GEMM / implicit-GEMM, HIP-event timed on the launch stream), `accuracy` (the committed parity record), at N=1 in bf16 the
+same step in the two fp32-storage modes (child processes), and at N=1 `cpu_baseline` (the oracle restatement timed on the
+host cores, bounded sample).
 """
 import argparse
 import json
@@ -397,7 +400,8 @@ def hbm_families(workload):
 
 
 def gemm_roofline(step, workload):
-    """One more (eager) step with every GEMM launch bracketed by HIP events on the launch stream."""
+    """One more (eager) step with every GEMM launch bracketed by HIP events on the launch stream (--full; the per-shape table
+    CMDA_BENCH_GEMM_HIST and the launch record CMDA_BENCH_GEMM_LOG are written here)."""
     from cmda_amd import ops
     ops.GEMM_PROFILE = []
     step()
@@ -552,7 +556,7 @@ def run_dacs(args, rank, world, dev, dist):
     graph_mode = ('linear hipGraph segments replayed on two streams (runtime.SegmentedCapture); EMA update, control-block copy, '
                   'AdamW outside') if dacs._graph is not None else 'eager'
     dacs.disable_graph()                      # the roofline leg brackets every GEMM launch with events: eager
-    roofline = gemm_roofline(step, 'dacs') if rank == 0 else None
+    roofline = gemm_roofline(step, 'dacs') if rank == 0 and args.full else None
     if rank == 0:
         nparam = sum(p.numel() for p in dacs.model.parameters())
         value = B * world * args.steps / dt
@@ -577,18 +581,19 @@ def run_dacs(args, rank, world, dev, dist):
                                                'kernels, sparse time residual, block labels with 5 % ignore')},
                'losses': losses,
                'model_gflop_per_pair': GFLOP_PER_PAIR_UDA,
-               'model_tflops_achieved': round(GFLOP_PER_PAIR_UDA * value / 1e3 / world, 2),
-               'roofline': roofline}
-        out['schema'] = 3   # 2: x3_* (split-bf16) and exact_f32_* carry the fp32-storage modes; parity_mode_* = alias of x3_* (ADVICE r04); 3: + accuracy
-        out['accuracy'] = accuracy_block()   # per mode: distance to the oracle at this configuration (committed parity run)
-        if world == 1 and args.dtype == 'bf16' and not args.no_parity_mode:
-            # the children allocate a whole fp32 model each: hand the parent's cached activation blocks back first
-            import gc
-            gc.collect()
-            torch.cuda.empty_cache()
-            out.update(parity_mode_line(args))
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline_dacs(args.size)
+               'model_tflops_achieved': round(GFLOP_PER_PAIR_UDA * value / 1e3 / world, 2)}
+        if args.full:
+            out['roofline'] = roofline
+            out['schema'] = 3   # 2: x3_* (split-bf16) and exact_f32_* carry the fp32-storage modes; parity_mode_* = alias of x3_* (ADVICE r04); 3: + accuracy
+            out['accuracy'] = accuracy_block()   # per mode: distance to the oracle at this configuration (committed parity run)
+            if world == 1 and args.dtype == 'bf16' and not args.no_parity_mode:
+                # the children allocate a whole fp32 model each: hand the parent's cached activation blocks back first
+                import gc
+                gc.collect()
+                torch.cuda.empty_cache()
+                out.update(parity_mode_line(args))
+            if world == 1 and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline_dacs(args.size)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
@@ -604,8 +609,9 @@ def parity_mode_line(args):
     out = {}
     for key, dt, what in (('x3', 'f32x3', 'dtype f32x3: fp32 storage, split-bf16 (bf16 x 3) MFMA GEMMs, same step, 3 timed steps in a child process'),
                           ('exact_f32', 'f32', 'dtype f32: exact-fp32 MFMA GEMMs and fp32 storage, same step, 3 timed steps in a child process')):
-        cmd = [sys.executable, os.path.abspath(__file__), '--dtype', dt, '--steps', '3', '--warmup', '1', '--no-cpu-baseline',
-               '--no-parity-mode', '--data', args.data, '--size', str(args.size)]
+        # a plain run (no --full): the child's headline figure is all this line takes from it
+        cmd = [sys.executable, os.path.abspath(__file__), '--dtype', dt, '--steps', '3', '--warmup', '1', '--data', args.data,
+               '--size', str(args.size)]
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
             line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1]
@@ -671,7 +677,7 @@ def run_supervised(args, rank, world, dev, dist):
     if args.dump_outputs and rank == 0:   # the last timed step's results, before the roofline leg runs one more step
         dump_outputs(args.dump_outputs, dict(log_arrays(losses), **model_outputs('model', model)))
     loss_val = float(losses['decode.loss_seg'].item())
-    roofline = gemm_roofline(step, 'supervised') if rank == 0 else None
+    roofline = gemm_roofline(step, 'supervised') if rank == 0 and args.full else None
     if rank == 0:
         ms = dt / args.steps * 1e3
         value = B * world * args.steps / dt
@@ -685,10 +691,11 @@ def run_supervised(args, rank, world, dev, dist):
                           'drop_path_rate': 0.1, 'dropout_ratio': 0.1, 'optimizer': 'AdamW (fused, flat buffers)'},
                'final_loss': round(loss_val, 5),
                'model_gflop_per_image_fwd_bwd': round(3 * GFLOP_PER_IMAGE_FWD, 1),
-               'model_tflops_achieved': round(3 * GFLOP_PER_IMAGE_FWD * value / 1e3 / world, 2),
-               'roofline': roofline}
-        if world == 1 and not args.no_cpu_baseline:
-            out['cpu_baseline'] = cpu_baseline_supervised(args.size)
+               'model_tflops_achieved': round(3 * GFLOP_PER_IMAGE_FWD * value / 1e3 / world, 2)}
+        if args.full:
+            out['roofline'] = roofline
+            if world == 1 and not args.no_cpu_baseline:
+                out['cpu_baseline'] = cpu_baseline_supervised(args.size)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.destroy_process_group()
@@ -774,12 +781,17 @@ def main():
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'f32', 'f32x3'],
                     help='bf16 = the speed mode (the headline); f32 = exact-fp32 MFMA GEMMs; f32x3 = fp32 storage with split-bf16 (bf16 x 3) GEMMs, '
                          'the tolerance-meeting mode (runtime.set_gemm_x3)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the GEMM roofline (one more eager step), the accuracy '
+                         'record, the step in the two fp32-storage modes (dacs, bf16, one GPU: child processes) and the CPU '
+                         'oracle baseline (one GPU)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU oracle baseline')
     ap.add_argument('--workload', default='dacs', choices=['dacs', 'supervised'],
                     help="dacs = BASELINE.json configs[3]/[4] (the bench line the driver reads): one full CMDA UDA iteration per "
                          "step; supervised = configs[1] (MiT-B5 + DAFormer head fwd/bwd)")
     ap.add_argument('--no-graph', action='store_true', help='dacs: launch every kernel from Python instead of replaying the hipGraph')
-    ap.add_argument('--no-parity-mode', action='store_true', help='dacs: skip the second figure (the same step in the exact-fp32 mode)')
+    ap.add_argument('--no-parity-mode', action='store_true',
+                    help='dacs with --full: skip the same step in the two fp32-storage modes (f32x3, f32)')
     ap.add_argument('--dry-run', action='store_true', help='launch / rendezvous plumbing only (gloo, no GPU work): CPU tests')
     ap.add_argument('--force-reducer', action='store_true',
                     help='testing: run the gradient all-reduce path (RCCL, side stream, staged ranges) even with one rank')

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Forced (tile, stages) sweep of the LDS-DMA GEMM over the DACS step's own plain-view shapes (bench.py CMDA_BENCH_GEMM_HIST):
+"""Forced (tile, stages) sweep of the LDS-DMA GEMM over the DACS step's own plain-view shapes (CMDA_BENCH_GEMM_HIST of bench.py --full):
 per shape the time of every configuration, 40 back-to-back launches between two events (launch floor included: compare rows,
 not absolute numbers).  usage: python tools/gemm_sweep.py [hist.txt]"""
 import os

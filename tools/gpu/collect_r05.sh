@@ -7,11 +7,11 @@
 tag=${1:-r05final}
 out=gpurun_out/$tag
 mkdir -p $out
-python bench.py > $out/bench.json 2> $out/err_bench
+python bench.py --full > $out/bench.json 2> $out/err_bench
 cut -c1-200 $out/bench.json
 alg=$(python -c "import json;print(json.loads(open('$out/bench.json').read().strip().splitlines()[-1])['roofline']['algorithmic_mb_per_launch'])")
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-B="--no-cpu-baseline --no-parity-mode"
+B="--full --no-cpu-baseline --no-parity-mode"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_graph -- python3 bench.py --steps 3 --warmup 1 $B > $out/bench_prof_graph.json 2> $out/err1
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_eager -- python3 bench.py --steps 3 --warmup 1 $B --no-graph > $out/bench_prof_eager.json 2> $out/err2
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/pmc_fetch -- python3 bench.py --steps 1 --warmup 1 $B --no-graph > $out/pmc_fetch.json 2> $out/err3
@@ -32,5 +32,5 @@ cp "$(ls -t $out/stats_x3/*/*kernel_stats.csv | head -1)" $out/x3_eager_kernel_s
 # the RCCL path with ONE rank (gradient exchange armed, reduce-scatter + all-gather of every bucket on the side stream)
 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --force-reducer $B > $out/bench_force_reducer.json 2> $out/err6
 cut -c1-200 $out/bench_force_reducer.json
-timeout 600 python bench.py --workload supervised --no-cpu-baseline > $out/supervised.json 2> $out/err_sup; cut -c1-200 $out/supervised.json
+timeout 600 python bench.py --full --workload supervised --no-cpu-baseline > $out/supervised.json 2> $out/err_sup; cut -c1-200 $out/supervised.json
 ls $out

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Which GEMM kernel instances over-fetch?  Folds the FETCH_SIZE / WRITE_SIZE passes of one bench.py command per kernel INSTANCE
 (template instantiation) and sets the measured bytes against the algorithmic bytes of the launches that ran on it: the bench's own
-launch-ordered GEMM record of its last (eager) step (CMDA_BENCH_GEMM_LOG) is matched, dispatch by dispatch, with the 'gemm' dispatches
-of the last step of each counter pass (the passes run the same deterministic launch sequence).
+launch-ordered GEMM record of its last (eager) step (CMDA_BENCH_GEMM_LOG, written by the roofline step of `bench.py --full`) is
+matched, dispatch by dispatch, with the 'gemm' dispatches of the last step of each counter pass (the passes run the same
+deterministic launch sequence).
 Corrections as in pmc_traffic.py: KiB units, FETCH_SIZE x 2 on gfx950 (MI355X_MICROARCH.md, HBM section).
 usage: pmc_gemm_instances.py <fetch_dir> <write_dir> <gemm_log.json> <out.txt>"""
 import collections
@@ -33,7 +34,7 @@ def main():
     fetch_dir, write_dir, log, out = sys.argv[1:5]
     fe, wr = last_step_gemms(fetch_dir, 'FETCH_SIZE'), last_step_gemms(write_dir, 'WRITE_SIZE')
     rec = json.load(open(log))
-    lines = ['rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python3 bench.py --steps 1 --warmup 1 --no-graph '
+    lines = ['rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) over `python3 bench.py --full --steps 1 --warmup 1 --no-graph '
              '--no-cpu-baseline --no-parity-mode`, last step; per GEMM kernel instance: measured HBM-side bytes (FETCH x 2 + WRITE) against the',
              'algorithmic bytes (operand tensors once + output) of the launches that ran on it (bench.py CMDA_BENCH_GEMM_LOG, matched in launch order)', '']
     # a GROUPED record of the bench (one cmda_gemm_grouped flush = the deferred weight gradients of a backward phase) is several
