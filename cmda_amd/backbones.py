@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from . import nn as K
-from . import ops
+from . import deferred, ops
 from . import runtime as rt
 from .registry import BACKBONES
 
@@ -309,8 +309,8 @@ class MixVisionTransformer(nn.Module):
             # used in the first part of the iteration are idle by now (runtime.LANE_ALIAS).  With a gradient exchange armed the stage's
             # gradients must be final here: flushed in place.
             if rt.grad_ready_hook is None:
-                src_lane = ops.LN_LANE
-                with rt.lane('wq', *ops.gemm_deferred_tensors()):
+                src_lane = deferred.LANES[-1]
+                with rt.lane('wq', *deferred.queued_tensors()):
                     ops.gemm_flush_deferred(from_lane=src_lane)
             else:
                 ops.gemm_flush_deferred()

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import nn as K
-from . import ops
+from . import deferred, ops
 from . import runtime as rt
 from .registry import HEADS, LOSSES, build_loss
 
@@ -139,8 +139,8 @@ class ASPPWrapper(nn.Module):
                 dub = K.linear_bwd(dz, ub, pwm.conv.weight, None, M, Cin)
                 du = _bn_bwd(dwm.bn, dub, u, st_u, M, Cin, True, groups=groups)
                 # (off the critical path: with a tail queue open -- segmentors.train_bwd -- it runs in the tail of the backward pass)
-                ops.tail_defer(lambda du=du, gw=rt.grad(dwm.conv.weight).view(Cin, 9), d=d:
-                               ops.dwconv_bwd_weight(du, x, gw, None, B, H, W, Cin, d))
+                deferred.tail_defer(lambda du=du, gw=rt.grad(dwm.conv.weight).view(Cin, 9), d=d:
+                                    ops.dwconv_bwd_weight(du, x, gw, None, B, H, W, Cin, d))
                 ops.dwconv_bwd_data(du, rt.wdw(dwm.conv.weight), B, H, W, Cin, d, out=dx, accumulate=not first)
             first = False
         return dx

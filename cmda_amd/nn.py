@@ -76,7 +76,7 @@ def conv_bwd(dy, x, weight, bias, B, H, W, stride, pad, dil=1, *, need_dx=True, 
     Co, Ci, KH, KW = weight.shape
     if ci_pad > Ci:   # channel-padded input (the encoder's first convolution): weight gradient through a padded shadow, no dx
         assert not need_dx
-        with ops.ln_deferral():   # (a scope of its own when called outside a backward pass: the shadow is drained on exit)
+        with ops.backward_scope():   # (a scope of its own when called outside a backward pass: the shadow is drained on exit)
             return _conv_bwd(dy, x, weight, bias, B, H, W, stride, pad, dil, need_dx=False, ci_pad=ci_pad)
     return _conv_bwd(dy, x, weight, bias, B, H, W, stride, pad, dil, need_dx=need_dx, dx_out=dx_out, dx_beta=dx_beta)
 
@@ -87,7 +87,7 @@ def _conv_bwd(dy, x, weight, bias, B, H, W, stride, pad, dil=1, *, need_dx=True,
     OH, OW = conv_out_size(H, W, KH, stride, pad, dil)
     M, K = B * OH * OW, KH * KW * Ci
     def wgrad():
-        # dW[co, (kh,kw,ci)] accumulated with atomics; outside a deferral scope straight into the parameter's [Co,Ci,KH,KW]
+        # dW[co, (kh,kw,ci)] accumulated with atomics; outside a backward scope straight into the parameter's [Co,Ci,KH,KW]
         # gradient (c_perm: no staging buffer); the bias gradient rides along in the same kernel when the operands allow
         dyv = plain_view(dy, M, Co)
         fused = (bias is not None and rt.tag() == 1 and dyv.vec_ok and Co % 8 == 0 and K % 8 == 0 and Ci % 8 == 0)

@@ -3,9 +3,11 @@ differentiable building blocks live in cmda_amd/functional.py and call these for
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from . import _lib as L
+from . import deferred as D
 from ._lib import BF16, F32, GemmParams, View, c_f32, c_i32, c_i64, call, check_dev, dtype_tag, ptr, stream_of
 
 _ESIZE = {torch.float32: 4, torch.bfloat16: 2}
@@ -176,9 +178,9 @@ def gemm(A, B, out, M, N, K, *, a_kstrided=False, b_kstrided=False, ldc=None, ba
          rowscale=None, rows_per_scale=1, atomic=False, dtype=None, c_offset=0, colsum=None, c_patch=None, c_perm=None, defer=False, keep=(),
          hold=False, colstats=None):
     """out[m,n] = epi(alpha * sum_k A(m,k) B(n,k)); A/B are `View`s built by plain_view / conv_view.
-    defer=True (weight gradients: nothing reads `out` before the pass ends): inside a deferral scope (`ln_deferral`) the launch is
-    only QUEUED and goes out with the next `gemm_flush_deferred()` as part of a grouped launch; `keep` = the tensors behind the
-    operand views (kept alive until then).
+    defer=True (weight gradients: nothing reads `out` before the pass ends): inside a `backward_scope` the launch is only QUEUED
+    and goes out with the next `gemm_flush_deferred()` as part of a grouped launch; `keep` = the tensors behind the operand views
+    (kept alive until then).
     hold=True: build the problem but do NOT launch it -- returns (params, meta, out, keep) for tools that time or inspect it.
     colstats=(ws, rows_per_group): column sums / sums of squares of the stored output accumulated into the BatchNorm workspace `ws`
     (`bn_stats_ws`: zero on entry) by the epilogue -- the statistics pass of the BatchNorm / InstanceNorm behind this convolution
@@ -234,11 +236,10 @@ def gemm(A, B, out, M, N, K, *, a_kstrided=False, b_kstrided=False, ldc=None, ba
         # deferred problems are launched AFTER the grouped ones of their flush whatever their list position (cmda_gemm_grouped): only
         # commutative accumulation may be deferred
         assert atomic and beta == 0.0, 'ops.gemm(defer=True) is for atomic accumulation only'
-    if defer and _LN_DEFER['depth'] > 0 and GEMM_DEFER:
+    if defer and D.depth > 0 and GEMM_DEFER:
         es = 2 if dtype == 1 else 4
         nb = batch * batch2
-        _GD['queues'].setdefault(GD_QUEUE_KEY or LN_LANE, []).append((p, (out, colsum) + tuple(keep), 2.0 * M * N * K * nb,
-                                                      (M * K + N * K) * nb * es + 2 * M * N * nb * 4, GEMM_SITE))
+        D.enqueue((p, (out, colsum) + tuple(keep), 2.0 * M * N * K * nb, (M * K + N * K) * nb * es + 2 * M * N * nb * 4, GEMM_SITE))
         return out
     if hold or (GEMM_PROFILE is not None and out.is_cuda):
         es = 2 if dtype == 1 else 4
@@ -261,82 +262,15 @@ def gemm(A, B, out, M, N, K, *, a_kstrided=False, b_kstrided=False, ldc=None, ba
     return out
 
 
-# ---- deferred weight gradients: queued by gemm(defer=True) inside a deferral scope, launched in groups (cmda_gemm_grouped) ----------
-import os as _os
-# queue key override for gemm(defer=True) (None: the current lane).  The decode head's weight gradients are queued under their own
-# key when they are to run in the TAIL of the backward pass (segmentors.train_bwd): the per-stage flushes of the encoders' backward
-# passes, which run on the same lane in between, must not launch them.
-GD_QUEUE_KEY = None
-# work postponed to the same tail (closures: the head's depthwise weight-gradient kernels), run by `run_tail()`
-_TAIL_FNS = []
-GEMM_DEFER = _os.environ.get('CMDA_GEMM_DEFER', '1') != '0'    # False: defer=True launches in place (A/B switch for tuning, tests of the single-launch path)
-_GD = {'queues': {}, 'plans': {}, 'arena': None, 'pinned_plans': False}
-_GD_ARENA_BYTES = 192 << 20
-_GD_EAGER_ARENA_BYTES = 64 << 20
-
-
-def _gd_arena(dev, nbytes):
-    """slice of the pinned host arena the grouped launches' tables are built in (a plain CPU tensor under the emulator).
-    Two arenas: the MAIN one holds every plan made before or inside a capture -- a captured graph re-runs the upload kernel of its
-    plans on every replay, so its slices are never reused; once a capture has pinned plans, EAGER plans made afterwards (backward
-    passes whose operand pointers differ from the captured ones: allocator churn, another batch shape's warm-up) live in a second,
-    RECYCLABLE arena that is rewound (one sync, un-captured plans dropped) when it fills -- pinned host memory stays bounded at two
-    arenas whatever the training run does (one retired 192 MB arena per exhaustion before).  `_GD['recycles']` counts
-    the rewinds."""
-    nbytes = (nbytes + 255) // 256 * 256
-    capturing = dev.type == 'cuda' and torch.cuda.is_current_stream_capturing()
-    pin = dev.type == 'cuda'
-    if _GD['pinned_plans'] and not capturing:
-        a = _GD.get('eager_arena')
-        if a is None or a[0].numel() < nbytes:
-            a = _GD['eager_arena'] = [torch.empty(max(_GD_EAGER_ARENA_BYTES, nbytes), dtype=torch.uint8, pin_memory=pin), 0]
-        if a[1] + nbytes > a[0].numel():
-            if pin:
-                torch.cuda.synchronize(dev)   # every upload that read the eager arena has run
-            _GD['plans'] = {k: v for k, v in _GD['plans'].items() if v[3]}
-            a[1] = 0
-            _GD['recycles'] = _GD.get('recycles', 0) + 1
-        lo = a[1]
-        a[1] = lo + nbytes
-        return a[0][lo:lo + nbytes], True
-    a = _GD['arena']
-    if a is None:
-        if capturing:
-            raise RuntimeError('grouped-GEMM arena: run one eager backward pass before capturing')
-        a = _GD['arena'] = [torch.empty(_GD_ARENA_BYTES, dtype=torch.uint8, pin_memory=pin), 0]
-    if a[1] + nbytes > a[0].numel():
-        if capturing or _GD['pinned_plans']:
-            raise RuntimeError('grouped-GEMM arena exhausted by captured plans: raise ops._GD_ARENA_BYTES')
-        if pin:
-            torch.cuda.synchronize(dev)   # eager plans only: every upload that read the arena has run
-        _GD['plans'].clear()
-        a[1] = 0
-    lo = a[1]
-    a[1] = lo + nbytes
-    return a[0][lo:lo + nbytes], False
-
-
-def tail_defer(fn):
-    """run fn() now -- or, while a tail queue is open (GD_QUEUE_KEY set inside a deferral scope), together with that queue"""
-    if GD_QUEUE_KEY is not None and _LN_DEFER['depth'] > 0:
-        _TAIL_FNS.append(fn)
-    else:
-        fn()
+# ---- deferred weight gradients: queued by gemm(defer=True) inside a backward scope, launched in groups (cmda_gemm_grouped) -----
+GEMM_DEFER = os.environ.get('CMDA_GEMM_DEFER', '1') != '0'    # False: defer=True launches in place (A/B switch for tuning, tests of the single-launch path)
 
 
 def run_tail(key):
-    """launch everything postponed under `key`: the queued weight gradients (grouped launch) and the postponed closures"""
-    fns = list(_TAIL_FNS)
-    del _TAIL_FNS[:]
-    for fn in fns:
+    """launch everything postponed under `key` (deferred.queue_under): the closures, then the queued weight gradients"""
+    for fn in D.TAIL.pending.pop(key, ()):
         fn()
     gemm_flush_deferred(from_lane=key)
-
-
-def gemm_deferred_tensors(lane=None):
-    """the tensors behind the queued problems of `lane` (default: the current one) -- what a side lane that launches them must keep alive"""
-    lane = LN_LANE if lane is None else lane
-    return [t for e in _GD['queues'].get(lane, ()) for t in e[1] if t is not None]
 
 
 def gemm_flush_deferred(all_lanes=False, from_lane=None):
@@ -344,32 +278,16 @@ def gemm_flush_deferred(all_lanes=False, from_lane=None):
     producers may still be running on their stream), every queue with all_lanes (after the lanes were joined).  from_lane: launch
     THAT lane's queue from here (a side lane entered behind the producers: the decode head's weight gradients next to the encoders'
     backward pass, segmentors.train_bwd)."""
-    if from_lane is not None:
-        lanes = [k for k in _GD['queues'] if k == from_lane or k.startswith(from_lane + '/wgrad')]
-    else:
-        lanes = list(_GD['queues']) if all_lanes else [k for k in _GD['queues'] if k == LN_LANE or k.startswith(LN_LANE + '/wgrad')]
-    for lane in lanes:
-        q = _GD['queues'].pop(lane, None)
+    lane = from_lane if from_lane is not None else (None if all_lanes else D.LANES[-1])
+    for key in D.select(D.GEMM.pending, lane):
+        q = D.GEMM.pending.pop(key, None)
         if not q:
             continue
         n = len(q)
         arr = (GemmParams * n)(*[e[0] for e in q])
         out0 = q[0][1][0]
-        dev = out0.device
-        key = (str(dev), bytes(arr))
-        plan = _GD['plans'].get(key)
-        upload = 0
-        capturing = dev.type == 'cuda' and torch.cuda.is_current_stream_capturing()
-        if plan is not None and capturing and plan[4]:
-            plan = None   # made eagerly in the recyclable arena: a captured graph needs a slice that stays -> rebuild it in the main one
-        if plan is None:
-            nbytes = int(L.lib().cmda_gemm_grouped_ws_bytes(arr, c_i32(n)))
-            host, recyclable = _gd_arena(dev, max(nbytes, 16))
-            plan = _GD['plans'][key] = [host, torch.empty(max(nbytes, 16), dtype=torch.uint8, device=dev), nbytes, False, recyclable]
-            upload = 1
-        if capturing:
-            _GD['pinned_plans'] = True
-            plan[3] = True    # a captured graph replays this plan's upload + launch: its arena slice and device table stay
+        plan, upload = D.gemm_plan((str(out0.device), bytes(arr)), out0.device,
+                                   lambda: int(L.lib().cmda_gemm_grouped_ws_bytes(arr, c_i32(n))))
         host, devbuf, nbytes = plan[:3]
         prof = GEMM_PROFILE is not None and out0.is_cuda
         if prof:
@@ -397,186 +315,73 @@ def layernorm_fwd(x, gamma, beta, eps, save_stats=True, out=None, out_dtype=None
     return y, mean, rstd
 
 
-_LN_WS = {}
-_LN_WS_MAX = {}
-LN_LANE = 'main'   # set by runtime.lane: LayerNorm backward passes running side by side must not share one workspace
+class backward_scope:
+    """A backward pass: inside it the LayerNorm parameter gradients, the conv weight-gradient shadows, the weight-gradient GEMMs and
+    the tail closures are deferred (flush_deferred launches them).  The outermost exit, which follows the lanes' joins, launches
+    what is left on every lane -- or drops it when the pass raised."""
 
-
-def _ln_ws(device, n):
-    """persistent zero-initialised LayerNorm-backward workspace (the kernel pair leaves it zeroed; calls on one stream are
-    ordered, so one buffer per device and concurrency lane is enough)"""
-    dkey = (device.type, device.index)
-    _LN_WS_MAX[dkey] = max(_LN_WS_MAX.get(dkey, 64 * 2 * 1024), n)
-    key = dkey + (LN_LANE,)
-    ws = _LN_WS.get(key)
-    if ws is None or ws.numel() < n:
-        ws = _LN_WS[key] = torch.zeros(_LN_WS_MAX[dkey], dtype=torch.float32, device=device)
-    return ws
-
-
-def ln_ws_prealloc(device, lanes):
-    """create the workspaces of the given lanes NOW (eagerly), sized for the largest request seen so far -- so that a graph
-    capture never allocates one from its private pool"""
-    dkey = (device.type, device.index)
-    n = _LN_WS_MAX.get(dkey, 64 * 2 * 1024)
-    for ln in lanes:
-        key = dkey + (ln,)
-        if key not in _LN_WS or _LN_WS[key].numel() < n:
-            _LN_WS[key] = torch.zeros(n, dtype=torch.float32, device=device)
-
-
-# Deferred LayerNorm parameter gradients: inside `ln_deferral()` every layernorm_bwd leaves its per-block partial sums in a
-# workspace owned by that layer (keyed by its dgamma buffer) and ONE cmda_layernorm_fold_batch launch at the end of the scope
-# folds all of them into dgamma / dbeta -- the ~700 finalize launches per UDA step this replaces only fed the optimizer.
-_LN_DEFER = {'depth': 0, 'regions': {}, 'touched': {}, 'plans': {}}
-
-
-_ARENA = {}
-
-
-def _host_table(raw, dev):
-    """A small descriptor table the kernels read in place.  On the GPU it lives in PINNED HOST memory (a few KB per launch over the
-    bus): a new set of layers may show up while a stream is capturing (the per-lane folds of a segmented capture differ from the
-    eager iteration's), and neither a host-to-device copy nor an allocation is capturable -- a slice of an arena allocated up
-    front is."""
-    if dev.type != 'cuda':
-        return raw
-    arena = _ARENA.get('a')
-    if arena is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('descriptor arena: run one eager backward pass before capturing')
-        arena = _ARENA['a'] = [torch.empty(16 << 20, dtype=torch.uint8, pin_memory=True), 0]
-    lo = arena[1]
-    if lo + raw.numel() > arena[0].numel():
-        raise RuntimeError('descriptor arena exhausted')
-    tab = arena[0][lo:lo + raw.numel()]
-    tab.copy_(raw)   # host-to-host
-    arena[1] = lo + (raw.numel() + 63) // 64 * 64
-    return tab
-
-
-class ln_deferral:
     def __enter__(self):
-        _LN_DEFER['depth'] += 1
+        D.depth += 1
         return self
 
     def __exit__(self, *exc):
-        _LN_DEFER['depth'] -= 1
-        if _LN_DEFER['depth'] == 0:
+        D.depth -= 1
+        if D.depth == 0:
             if exc[0] is None:
-                fns = list(_TAIL_FNS)   # (a tail nobody ran: run it here)
-                del _TAIL_FNS[:]
-                for fn in fns:
-                    fn()
-                ln_fold_deferred(all_lanes=True)
+                for key in list(D.TAIL.pending):   # (a tail nobody ran: run it here)
+                    for fn in D.TAIL.pending.pop(key):
+                        fn()
+                flush_deferred(all_lanes=True)
             else:   # the pass died half way: drop what it queued / touched instead of folding it into the next pass
-                del _TAIL_FNS[:]
-                _LN_DEFER['touched'] = {}
-                _CG['touched'] = {}
-                _GD['queues'].clear()
+                D.reset()
         return False
 
 
-def _take_lanes(store, all_lanes):
-    """pop the entries of the CURRENT lane and of the lanes forked below it that were joined back (`<lane>/wgrad...`: the
-    batched weight-gradient closures of runtime.lane_batch register their work there) -- or of every lane"""
-    if all_lanes:
-        keys = list(store)
-    else:
-        keys = [k for k in store if k == LN_LANE or k.startswith(LN_LANE + '/wgrad')]
-    out = {}
-    for k in keys:
-        out.update(store.pop(k))
-    return out
+def _ln_fold_plan(dev, regions):
+    desc = np.zeros(len(regions), dtype=[('ws', '<u8'), ('dg', '<u8'), ('db', '<u8'), ('C', '<i4'), ('n', '<i4')])
+    for i, (ws, dg, db, C, nslots) in enumerate(regions):
+        desc[i] = (ws.data_ptr(), dg.data_ptr(), db.data_ptr(), C, nslots)
+    return D.host_table(desc, dev), len(regions), max(r[3] for r in regions)
 
 
-def _ln_region(dgamma, dbeta, C):
-    key = dgamma.data_ptr()
-    r = _LN_DEFER['regions'].get(key)
-    if r is None or r[0].device != dgamma.device:
-        nslots = L.lib().cmda_layernorm_slots()
-        r = _LN_DEFER['regions'][key] = (torch.zeros(nslots * 2 * C, dtype=torch.float32, device=dgamma.device), dgamma, dbeta, C, nslots)
-    _LN_DEFER['touched'].setdefault(LN_LANE, {})[key] = r
-    return r[0]
+def _conv_drain_plan(dev, shadows):
+    desc = np.zeros(len(shadows), dtype=[('src', '<u8'), ('dst', '<u8'), ('d', '<i4', 4), ('p', '<i4', 4), ('flip', '<i4'),
+                                         ('mode', '<i4'), ('total', '<i8')])
+    blocks = []
+    for i, (sh, g) in enumerate(shadows):
+        Co, Ci, KH, KW = g.shape
+        cs = sh.shape[1] // (KH * KW)   # channels of the shadow (> Ci: padded)
+        desc[i] = (sh.data_ptr(), g.data_ptr(), (Co, KH, KW, cs), (0, 3, 1, 2), ((4 << 8) | (Ci << 16)) if cs != Ci else 0, 2, g.numel())
+        blocks += [(i, b) for b in range((g.numel() + 1023) // 1024)]
+    return D.host_table(desc, dev), D.host_table(np.asarray(blocks, dtype=np.int32), dev), len(blocks)
 
 
-def ln_fold_deferred(all_lanes=False):
-    """fold every workspace touched since the last fold into its dgamma / dbeta: one launch per device.  Only the CURRENT
-    concurrency lane's workspaces by default (another lane's LayerNorm backward kernels may still be running on their stream);
-    the end of the scope, which follows the lanes' joins, folds them all."""
+def flush_deferred(all_lanes=False):
+    """launch the queued weight gradients, then drain the conv shadows and fold the LayerNorm partial sums (one launch per device
+    each).  Only the CURRENT concurrency lane's work by default: another lane's kernels may still be running on their stream."""
+    lane = None if all_lanes else D.LANES[-1]
     gemm_flush_deferred(all_lanes)   # queued weight gradients first: the convolution ones land in the shadows drained next
-    conv_grad_drain(all_lanes)
-    touched = _take_lanes(_LN_DEFER['touched'], all_lanes)
-    if not touched:
-        return
-    import numpy as np
-    by_dev = {}
-    for key, r in touched.items():
-        by_dev.setdefault(r[0].device, []).append((key, r))
-    for dev, items in by_dev.items():
-        items.sort(key=lambda kv: kv[0])
-        pkey = (dev, tuple(k for k, _ in items))
-        plan = _LN_DEFER['plans'].get(pkey)
-        if plan is None:
-            desc = np.zeros(len(items), dtype=[('ws', '<u8'), ('dg', '<u8'), ('db', '<u8'), ('C', '<i4'), ('n', '<i4')])
-            for i, (_, (ws, dg, db, C, nslots)) in enumerate(items):
-                desc[i] = (ws.data_ptr(), dg.data_ptr(), db.data_ptr(), C, nslots)
-            tab = _host_table(torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()), dev)
-            plan = _LN_DEFER['plans'][pkey] = (tab, len(items), max(r[3] for _, r in items), dev)
-        call('cmda_layernorm_fold_batch', ptr(plan[0]), c_i32(plan[1]), c_i32(plan[2]), stream_of(items[0][1][0]))
+    for (tab, blk, nblocks), t in D.launch_plans(D.CONV, lane, _conv_drain_plan):
+        call('cmda_permute4_batch', ptr(tab), ptr(blk), c_i32(nblocks), stream_of(t))
+    for (tab, n, max_c), t in D.launch_plans(D.LN, lane, _ln_fold_plan):
+        call('cmda_layernorm_fold_batch', ptr(tab), c_i32(n), c_i32(max_c), stream_of(t))
 
 
-# Deferred convolution weight gradients: inside the same scope a conv weight gradient is accumulated by the GEMM's atomics in the
+# Deferred convolution weight gradients: inside a backward scope a conv weight gradient is accumulated by the GEMM's atomics in the
 # GEMM's own column order (kh, kw, ci) -- coalesced -- into a persistent zeroed fp32 shadow [Co,KH,KW,Ci] of the parameter's
-# gradient, and ONE batched launch per fold point moves all shadows into the [Co,Ci,KH,KW] gradients and clears them (the
-# permuted atomic store it replaces cost 20-84 us per spatial-reduction conv against 10-14 us, tools/dbg/srconv_dbg.py).
-_CG = {'regions': {}, 'touched': {}, 'plans': {}}
-
-
+# gradient, and ONE batched launch per flush moves all shadows into the [Co,Ci,KH,KW] gradients and clears them (the permuted
+# atomic store it replaces cost 20-84 us per spatial-reduction conv against 10-14 us, tools/dbg/srconv_dbg.py).
 def conv_grad_shadow(grad, ci_pad=0):
-    """grad: fp32 [Co,Ci,KH,KW] parameter gradient -> its [Co, KH*KW*Ci] shadow, or None outside a deferral scope.  ci_pad > Ci:
+    """grad: fp32 [Co,Ci,KH,KW] parameter gradient -> its [Co, KH*KW*Ci] shadow, or None outside a backward scope.  ci_pad > Ci:
     the shadow carries the padded channels of the GEMM ([Co, KH*KW*ci_pad]); the drain keeps the real ones."""
     Co, Ci, KH, KW = grad.shape
     if ci_pad <= Ci and not grad.is_contiguous() and grad.permute(0, 2, 3, 1).is_contiguous():
         # channels-last stored gradient (optim.FlatAdamW): its memory is the GEMM's own [Co][KH][KW][Ci] order -- accumulate in place,
         # nothing to drain
         return grad.permute(0, 2, 3, 1).reshape(Co, KH * KW * Ci)
-    if _LN_DEFER['depth'] == 0:
+    if D.depth == 0:
         return None
-    key = grad.data_ptr()
-    r = _CG['regions'].get(key)
-    cs = max(Ci, ci_pad)
-    if r is None or r[0].device != grad.device or r[0].shape[1] != KH * KW * cs:
-        r = _CG['regions'][key] = (torch.zeros(Co, KH * KW * cs, dtype=torch.float32, device=grad.device), grad)
-    _CG['touched'].setdefault(LN_LANE, {})[key] = r
-    return r[0]
-
-
-def conv_grad_drain(all_lanes=False):
-    touched = _take_lanes(_CG['touched'], all_lanes)
-    if not touched:
-        return
-    import numpy as np
-    by_dev = {}
-    for key, r in touched.items():
-        by_dev.setdefault(r[0].device, []).append((key, r))
-    for dev, items in by_dev.items():
-        items.sort(key=lambda kv: kv[0])
-        pkey = (dev, tuple(k for k, _ in items))
-        plan = _CG['plans'].get(pkey)
-        if plan is None:
-            desc = np.zeros(len(items), dtype=[('src', '<u8'), ('dst', '<u8'), ('d', '<i4', 4), ('p', '<i4', 4), ('flip', '<i4'),
-                                               ('mode', '<i4'), ('total', '<i8')])
-            blocks = []
-            for i, (_, (sh, g)) in enumerate(items):
-                Co, Ci, KH, KW = g.shape
-                cs = sh.shape[1] // (KH * KW)   # channels of the shadow (> Ci: padded)
-                desc[i] = (sh.data_ptr(), g.data_ptr(), (Co, KH, KW, cs), (0, 3, 1, 2), ((4 << 8) | (Ci << 16)) if cs != Ci else 0, 2, g.numel())
-                blocks += [(i, b) for b in range((g.numel() + 1023) // 1024)]
-            tab = _host_table(torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()), dev)
-            blk = _host_table(torch.from_numpy(np.asarray(blocks, dtype=np.int32).reshape(-1).view(np.uint8).copy()), dev)
-            plan = _CG['plans'][pkey] = (tab, blk, len(blocks))
-        call('cmda_permute4_batch', ptr(plan[0]), ptr(plan[1]), c_i32(plan[2]), stream_of(items[0][1][0]))
+    return D.conv_shadow(grad, KH * KW * max(Ci, ci_pad))
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, dres=None, out_scale=None, rows_per_scale=0):
@@ -586,10 +391,10 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, dres=None, out_scale=
     rows = x.numel() // C
     dx = torch.empty_like(dy)       # (x may be the fp32 residual stream while the gradients travel in the compute dtype)
     dxs = torch.empty_like(dy) if out_scale is not None else None
-    if _LN_DEFER['depth'] > 0:
-        ws, dg, db = _ln_region(dgamma, dbeta, C), None, None
+    if D.depth > 0:   # (backward scope: partial sums into the layer's region, folded by flush_deferred)
+        ws, dg, db = D.ln_region(dgamma, dbeta, C), None, None
     else:
-        ws, dg, db = _ln_ws(x.device, L.lib().cmda_layernorm_bwd_ws_floats(rows, C)), dgamma, dbeta
+        ws, dg, db = D.workspace('ln', x.device, L.lib().cmda_layernorm_bwd_ws_floats(rows, C)), dgamma, dbeta
     call('cmda_layernorm_bwd2', ptr(dy), ptr(x), dtype_tag(x), ptr(gamma), ptr(mean), ptr(rstd), ptr(dres), ptr(dx), ptr(dg),
          ptr(db), ptr(ws), c_i64(rows), c_i32(C), ptr(out_scale), c_i64(rows_per_scale), ptr(dxs), dtype_tag(dy), stream_of(x))
     return dx if out_scale is None else (dx, dxs)
@@ -659,24 +464,10 @@ def permute4_batch(desc, blocks, nblocks):
     call('cmda_permute4_batch', ptr(desc), ptr(blocks), c_i32(nblocks), stream_of(desc))
 
 
-_ZERO_WS = {}
-
-
 def zero_ws(device, n):
     """persistent fp32 accumulation workspace, ZERO on entry by contract: whoever accumulates into it drains it with cast_clear
-    (one buffer per device and concurrency lane; calls on one stream are ordered)"""
-    key = (device.type, device.index, LN_LANE)
-    ws = _ZERO_WS.get(key)
-    if ws is None or ws.numel() < n:
-        ws = _ZERO_WS[key] = torch.zeros(max(n, 1 << 20), dtype=torch.float32, device=device)
-    return ws[:n]
-
-
-def zero_ws_prealloc(device, lanes, n=1 << 22):
-    for ln in lanes:
-        key = (device.type, device.index, ln)
-        if key not in _ZERO_WS or _ZERO_WS[key].numel() < n:
-            _ZERO_WS[key] = torch.zeros(n, dtype=torch.float32, device=device)
+    (one buffer per device and concurrency lane: deferred.workspace)"""
+    return D.workspace('zero', device, n)[:n]
 
 
 def cast_clear(src32, dtype):
@@ -872,31 +663,15 @@ def bilinear_bwd(dy, dx, B, IH, IW, OH, OW, C, ldy=None, coff=0):
 
 
 BN_FUSED_STATS = os.environ.get('CMDA_BN_FUSED_STATS', '1') != '0'   # statistics of conv -> BN / IN pairs in the GEMM epilogue (A/B switch)
-_BN_WS = {}
-
-
 def bn_stats_ws(device, groups, C):
-    """the persistent ZERO workspace a GEMM epilogue accumulates BatchNorm statistics into (gemm(colstats=...)); bn_train_fwd /
-    bn_train_fwd2 with stats_ws hand it back zeroed, so one buffer per device and concurrency lane serves every layer (calls on one
-    stream are ordered).  None where the fused statistics are switched off."""
+    """the persistent per-lane ZERO workspace a GEMM epilogue accumulates BatchNorm statistics into (gemm(colstats=...));
+    bn_train_fwd / bn_train_fwd2 with stats_ws hand it back zeroed.  None where the fused statistics are switched off, and inside a
+    capture for a lane nobody pre-allocated for (the separate statistics pass)."""
     if not BN_FUSED_STATS:
         return None
-    n = 8 * int(L.lib().cmda_bn_ws_floats(2048))
     need = groups * int(L.lib().cmda_bn_ws_floats(C))
-    key = (device.type, device.index, LN_LANE)
-    ws = _BN_WS.get(key)
-    if ws is None or ws.numel() < need:
-        if device.type == 'cuda' and torch.cuda.is_current_stream_capturing():
-            return None   # (a lane nobody pre-allocated for, met inside a capture: the separate statistics pass)
-        ws = _BN_WS[key] = torch.zeros(max(n, need), dtype=torch.float32, device=device)
-    return ws[:need]
-
-
-def bn_ws_prealloc(device, lanes):
-    for ln in lanes:
-        key = (device.type, device.index, ln)
-        if key not in _BN_WS:
-            _BN_WS[key] = torch.zeros(8 * int(L.lib().cmda_bn_ws_floats(2048)), dtype=torch.float32, device=device)
+    ws = D.workspace('bn', device, need, make_in_capture=False)
+    return None if ws is None else ws[:need]
 
 
 def colstats_ok(rows_per_group, N):
@@ -1089,7 +864,6 @@ _ISR_LUT = {}
 def isr_lut(val_range, device):
     """float32 log-intensity of the 256 gray levels, computed exactly as datasets/utils.py:get_ic does (numpy fp32); cached per
     (value range, device) -- the table is a constant of the configuration."""
-    import numpy as np
     key = (float(val_range[0]), float(val_range[1]), str(device))
     lut = _ISR_LUT.get(key)
     if lut is None:
@@ -1117,7 +891,6 @@ def isr_from_gray(gray, val_range, threshold, clip_range, shift_pixel, shift_dir
     """get_image_change_from_pil after the gray conversion -> fp32 NCHW [B,3,H,W] in [-1,1].  `dirs_dev`: optional DEVICE
     int32 [ndir,2] holding the (dy,dx) shifts (then `shift_direction` only gives ndir); lets a captured launch sequence pick
     the direction per replay."""
-    import numpy as np
     check_dev(gray, dirs_dev)
     B, H, W = gray.shape
     span = np.log(val_range[1]) - np.log(val_range[0])
@@ -1174,7 +947,6 @@ def gaussian_taps(k, sigma, device=None):
 
 def blur_kernel_size(n):
     """dacs_transforms.py:86-93: kernel size from the image extent n"""
-    import numpy as np
     return int(np.floor(np.ceil(0.1 * n) - 0.5 + np.ceil(0.1 * n) % 2))
 
 

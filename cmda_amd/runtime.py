@@ -16,7 +16,7 @@ import weakref
 
 import torch
 
-from . import ops
+from . import deferred, ops
 
 _state = {'dtype': torch.float32}
 _cache = {}
@@ -314,7 +314,7 @@ def ones1(device):
 # default of the captured DACS iteration (uda.GRAPH_LANES).  Four streams = HIP's four hardware queues: every lane stream is chosen so
 # that it really runs beside the others (prepare_lane_streams; two torch streams may share a queue), and GPU_MAX_HW_QUEUES=8 ran the
 # same four-lane step at 82-85 ms.
-_conc = {'on': False, 'streams': {}, 'stack': ['main'], 'sstack': [], 'used': {}, 'keep': {}, 'enabled': {'enc'}, 'seg': None, 'seen': set()}
+_conc = {'on': False, 'streams': {}, 'sstack': [], 'used': {}, 'keep': {}, 'enabled': {'enc'}, 'seg': None, 'seen': set()}
 
 
 class SegmentedCapture:
@@ -440,9 +440,9 @@ def set_concurrency(flag, lanes=None, seg=None):
         _conc['enabled'] = set(lanes)
     _conc['on'] = bool(flag)
     _conc['seg'] = seg if flag else None
-    _conc['stack'], _conc['used'], _conc['keep'], _conc['seen'], _conc['batch'] = ['main'], {}, {}, set(), None
+    _conc['used'], _conc['keep'], _conc['seen'], _conc['batch'] = {}, {}, set(), None
     _conc['sstack'] = [seg.main] if (flag and seg is not None) else []
-    ops.LN_LANE = 'main'
+    deferred.LANES[:] = ['main']
 
 
 def concurrency():
@@ -450,7 +450,7 @@ def concurrency():
 
 
 def lane_enabled(name):
-    return _conc['on'] and name in _conc['enabled'] and _conc['stack'][-1] == 'main'
+    return _conc['on'] and name in _conc['enabled'] and deferred.LANES[-1] == 'main'
 
 
 # Lanes that REUSE another lane's stream (and with it its hardware queue: HIP has four by default and more cost dearly -- GPU_MAX_HW_QUEUES=8
@@ -478,7 +478,7 @@ class lane:
     def __enter__(self):
         if not _conc['on'] or self.name not in _conc['enabled']:
             return self
-        parent = _conc['stack'][-1]
+        parent = deferred.LANES[-1]
         if self.name == 'enc' and parent != 'main' and 'Tenc' not in _conc['enabled']:
             return self   # the teacher's encoders on lane T run one after the other ('Tenc': side by side on a fourth queue, main/T/enc)
         seg = _conc['seg']
@@ -490,8 +490,7 @@ class lane:
             s = _conc['streams'][key] = torch.cuda.Stream(dev)
         _conc['used'][full] = s
         _conc['keep'].setdefault(full, []).extend(self.keep)
-        _conc['stack'].append(full)
-        ops.LN_LANE = full
+        deferred.LANES.append(full)
         self.on = True
         order = not (self.independent and full in _conc['seen'])
         _conc['seen'].add(full)
@@ -508,8 +507,7 @@ class lane:
     def __exit__(self, *exc):
         if self.on:
             seg = _conc['seg']
-            _conc['stack'].pop()
-            ops.LN_LANE = _conc['stack'][-1]
+            deferred.LANES.pop()
             if seg is not None:
                 _conc['sstack'].pop()
                 seg.cut(resume=_conc['sstack'][-1])
@@ -571,7 +569,7 @@ def wait_external(fn):
 
 def keep_alive(*tensors):
     if _conc['on']:
-        _conc['keep'].setdefault(_conc['stack'][-1], []).extend(tensors)
+        _conc['keep'].setdefault(deferred.LANES[-1], []).extend(tensors)
 
 
 def join_lanes(name=None):
@@ -579,7 +577,7 @@ def join_lanes(name=None):
     below it when no name is given; then release what those lanes kept alive"""
     if not _conc['on']:
         return
-    me = _conc['stack'][-1]
+    me = deferred.LANES[-1]
     root = me + '/' + name if name else None
 
     def hit(k):
@@ -624,7 +622,7 @@ def notify_grads_ready(tag, module=None):
     if hook is None:
         return
     join_lanes('wgrad')      # "final" includes the weight gradients still queued on the side lane ...
-    ops.ln_fold_deferred()   # "final" includes the LayerNorm parameter gradients still sitting in their workspaces
+    ops.flush_deferred()     # "final" includes the LayerNorm parameter gradients still sitting in their workspaces
     seg = _conc['seg']
     if seg is not None and seg.active is not None:
         seg.call(lambda: hook(tag, module))   # segmented capture: the hook becomes a host step of the replay program

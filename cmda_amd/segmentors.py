@@ -13,7 +13,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import deferred, ops
 from . import runtime as rt
 from .registry import SEGMENTORS, build_backbone, build_fusion, build_head
 
@@ -87,7 +87,7 @@ class EncoderDecoder(nn.Module):
 
     def train_bwd(self, saved, gscale):
         sv_b, sv_h, B = saved
-        with ops.ln_deferral():   # LayerNorm parameter gradients of the whole pass folded by one launch at the end
+        with ops.backward_scope():   # LayerNorm parameter gradients of the whole pass folded by one launch at the end
             dfs = self.decode_head.bwd_train(sv_h, B, gscale)
             rt.notify_grads_ready('decode_head', self.decode_head)
             self.backbone.bwd(sv_b, [dfs.get(i) for i in range(4)])
@@ -159,7 +159,7 @@ class EventsEncoderDecoder(EncoderDecoder):
         """img_grad_hook(d): called with the backbone's four output gradients before its backward pass starts; it may add into
         them in place, or fill a None entry (uda.DACS: the ImageNet feature distance on stage 4)"""
         sv_b, sv_h, B = saved
-        with ops.ln_deferral():
+        with ops.backward_scope():
             dfs = self.decode_head.bwd_train(sv_h, B, gscale)
             if rt.grad_ready_hook is not None:
                 ops.gemm_flush_deferred()   # the head's queued weight gradients are final before they are reported
@@ -455,7 +455,7 @@ class FusionEncoderDecoder(nn.Module):
 
     def train_bwd(self, saved, gscale, img_grad_hook=None):
         """img_grad_hook: see _extract_joint_bwd (the image encoder's output gradients, before its backward pass)"""
-        with ops.ln_deferral():   # LayerNorm parameter gradients of the whole pass folded by one launch at the end
+        with ops.backward_scope():   # LayerNorm parameter gradients of the whole pass folded by one launch at the end
             if saved[0] == 'joint':
                 _, sv, sv_h, B = saved[:4]
                 P = saved[4] if len(saved) > 4 else 1
@@ -466,19 +466,15 @@ class FusionEncoderDecoder(nn.Module):
                 # gradients must be final before the encoders start: flushed in place, as before.)
                 tail = (rt.concurrency() and rt.grad_ready_hook is None and not rt.lane_enabled('hw') and
                         os.environ.get('CMDA_HEAD_TAIL', '1') != '0')
-                if tail:
-                    ops.GD_QUEUE_KEY = 'main/headtail'
-                try:
+                with deferred.queue_under('main/headtail' if tail else None):
                     dJ = self.decode_head.bwd_train_joint(sv_h, B // P, gscale)
-                finally:
-                    ops.GD_QUEUE_KEY = None
                 if tail:
                     self._extract_joint_bwd(sv, dJ, B, tail_key='main/headtail', img_grad_hook=img_grad_hook)
                     return
                 if rt.lane_enabled('hw') and rt.grad_ready_hook is None:
                     # the decode head's queued weight gradients (dense 256 x 256-tile GEMMs, ~3.5 ms at 2 + 2 samples) are off the
                     # critical path: a third queue runs them underneath the encoders' latency-bound backward chains
-                    with rt.lane('hw', *ops.gemm_deferred_tensors()):
+                    with rt.lane('hw', *deferred.queued_tensors()):
                         ops.gemm_flush_deferred(from_lane='main')
                 else:
                     ops.gemm_flush_deferred()   # the decode head's queued weight gradients

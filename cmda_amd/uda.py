@@ -28,7 +28,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import deferred, ops
 from . import runtime as rt
 from .cyclegan import define_G
 from .parallel import reduce_log_vars
@@ -730,9 +730,7 @@ class DACS(nn.Module):
         st_tgt = {k: v.clone() for k, v in tgt.items() if isinstance(v, torch.Tensor)}
         second = torch.empty_like(st_src['image'])
         ws_lanes = ('main', 'main/enc', 'main/T', 'main/T/enc')   # (the per-lane persistent workspaces exist before the capture starts)
-        ops.ln_ws_prealloc(dev, ws_lanes)
-        ops.zero_ws_prealloc(dev, ws_lanes)
-        ops.bn_ws_prealloc(dev, ws_lanes)
+        deferred.prealloc(dev, ws_lanes)
         torch.cuda.synchronize(dev)
         rt.refresh(force=True)   # every copy exists and is current before the capture starts
         lanes = getattr(self, 'graph_lane_set', None)

@@ -3,7 +3,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from cmda_amd import ops
+from cmda_amd import deferred, ops
 from conftest import assert_close
 
 # tag 2 = CMDA_F32X3: fp32 storage, split-bf16 (bf16 x 3) MFMA -- ~16 mantissa bits per product (gemm_x3.hip)
@@ -265,7 +265,7 @@ def test_gemm_grouped_tile_walk(tgt, hint, M, N):
 
 @pytest.mark.parametrize('dt,tag', [(torch.bfloat16, 1), (torch.float32, 0), (torch.float32, 2)])
 def test_gemm_deferred_grouped_weight_gradients(tgt, dt, tag):
-    """ops.gemm(defer=True) inside a deferral scope queues the weight gradients of a backward pass and gemm_flush_deferred()
+    """ops.gemm(defer=True) inside a backward scope queues the weight gradients of a backward pass and gemm_flush_deferred()
     launches them as grouped grids (cmda_gemm_grouped: 64x64 ... 128x128 tiles and gemm_wg.hip's 256x256 tile, plain / patch / im2col B views, fused bias
     gradient, accumulation into non-zero gradients, deep contractions split by the planner); the fp32 parity mode and forced
     tiles fall back to single launches inside the same call.  Result == the same GEMMs launched one by one."""
@@ -301,13 +301,13 @@ def test_gemm_deferred_grouped_weight_gradients(tgt, dt, tag):
                 w.grad, b.grad = torch.full_like(w.data, 0.5), torch.full_like(b.data, -1.0)
             for _, _, w, b, _ in cvs:
                 w.grad, b.grad = torch.zeros_like(w.data), torch.zeros_like(b.data)
-            with ops.ln_deferral():
+            with ops.backward_scope():
                 for dy, x, w, b in lins:
                     K.linear_bwd(tgt.to(dy), tgt.to(x), w, b, dy.shape[0], x.shape[1], need_dx=False)
                 for dy, x, w, b, (Bc, H, W, st, pd) in cvs:
                     K.conv_bwd(tgt.to(dy), tgt.to(x.reshape(-1, x.shape[-1])), w, b, Bc, H, W, st, pd, need_dx=False)
-                assert bool(ops._GD['queues']) == bool(defer)
-            assert not ops._GD['queues']
+                assert bool(deferred.GEMM.pending) == bool(defer)
+            assert not deferred.GEMM.pending
             for _, _, w, b in lins:
                 grads += [w.grad.cpu().clone(), b.grad.cpu().clone()]
             for _, _, w, b, _ in cvs:
@@ -345,31 +345,32 @@ def test_gemm_deferred_grouped_weight_gradients(tgt, dt, tag):
 
 
 def test_grouped_gemm_eager_arena_recycles_after_a_capture(tgt):
-    """ops._gd_arena: once a capture has pinned plans, eager grouped launches build their tables in a second, recyclable arena that is
+    """deferred.gemm_plan: once a capture has pinned plans, eager grouped launches build their tables in a second, recyclable arena that is
     rewound when it fills -- no new pinned arena per exhaustion.  Simulated here by marking plans pinned and shrinking
     the eager arena: every flush still produces the right weight gradients and the rewinds are counted."""
     from cmda_amd import nn as K
     import cmda_amd.runtime as rt
     rt.set_compute_dtype(torch.bfloat16)
-    saved = (ops._GD['pinned_plans'], ops._GD.get('eager_arena'), ops._GD_EAGER_ARENA_BYTES, ops._GD.get('recycles', 0), dict(ops._GD['plans']))
+    A = deferred.GEMM_ARENAS
+    saved = (A['pinned_plans'], A['eager'], deferred.GEMM_EAGER_ARENA_BYTES, A['recycles'], dict(deferred.GEMM.plans))
     try:
-        ops._GD['pinned_plans'], ops._GD['eager_arena'], ops._GD_EAGER_ARENA_BYTES = True, None, 1024
+        A['pinned_plans'], A['eager'], deferred.GEMM_EAGER_ARENA_BYTES = True, None, 1024
         torch.manual_seed(9)
-        before = ops._GD.get('recycles', 0)
+        before = A['recycles']
         for rep in range(6):
             rows, n, k = 256 + 64 * rep, 64, 64    # a new problem (and plan key) every time
             dy, x = torch.randn(rows, n).bfloat16(), torch.randn(rows, k).bfloat16()
             w, b = torch.nn.Parameter(tgt.to(torch.randn(n, k))), torch.nn.Parameter(tgt.to(torch.randn(n)))
             w.grad, b.grad = torch.zeros_like(w.data), torch.zeros_like(b.data)
-            with ops.ln_deferral():
+            with ops.backward_scope():
                 K.linear_bwd(tgt.to(dy), tgt.to(x), w, b, rows, k, need_dx=False)
             assert_close(w.grad, dy.float().t() @ x.float(), 2e-2, name=f'dW after {rep} flushes')
-        assert ops._GD.get('recycles', 0) > before, 'the eager arena never filled: shrink it further'
-        assert ops._GD["eager_arena"][0].numel() <= 2048
+        assert A['recycles'] > before, 'the eager arena never filled: shrink it further'
+        assert A['eager'][0].numel() <= 2048
     finally:
-        ops._GD['pinned_plans'], ops._GD['eager_arena'], ops._GD_EAGER_ARENA_BYTES = saved[0], saved[1], saved[2]
-        ops._GD['recycles'] = saved[3]
-        ops._GD['plans'] = saved[4]
+        A['pinned_plans'], A['eager'], deferred.GEMM_EAGER_ARENA_BYTES = saved[0], saved[1], saved[2]
+        A['recycles'] = saved[3]
+        deferred.GEMM.plans = saved[4]
         rt.set_compute_dtype(torch.float32)
 
 
