@@ -326,7 +326,6 @@ class SegmentedCapture:
         self.main = torch.cuda.Stream(device)
         self.program = []      # ('replay', graph, stream) | ('wait', waiter, waited) | ('call', fn, stream)
         self.active = None
-        self.n_nodes = 0
 
     def begin(self, stream):
         g = torch.cuda.CUDAGraph()

@@ -37,6 +37,32 @@ def parse_losses(losses):
     return loss, log_vars
 
 
+def _first_meta(img_metas):
+    """the (first) image's meta dict; {} when there is none"""
+    return (img_metas[0] if isinstance(img_metas, (list, tuple)) else img_metas) or {}
+
+
+def _resize_logits(seg_logit, ori_shape):
+    """NCHW logits at the size ori_shape[:2] (the test pipeline's `rescale`)"""
+    h, w = ori_shape[:2]
+    if (h, w) != tuple(seg_logit.shape[2:]):
+        seg_logit = ops.upsample_logits_nchw(seg_logit.permute(0, 2, 3, 1).contiguous(), h, w)
+    return seg_logit
+
+
+def _flip_back(seg, meta):
+    """undo the test pipeline's flip"""
+    if meta.get('flip'):
+        assert meta['flip_direction'] in ('horizontal', 'vertical')
+        seg = seg.flip(dims=(3,) if meta['flip_direction'] == 'horizontal' else (2,))
+    return seg
+
+
+def _label_maps(seg):
+    """per-image label maps (numpy) from NCHW logits or probabilities"""
+    return list(seg.argmax(dim=1).cpu().numpy())
+
+
 class _TrainFn(torch.autograd.Function):
     """loss = runner.train_fwd(...); backward(dloss) -> runner.train_bwd(saved, dloss)."""
 
@@ -80,23 +106,29 @@ class EncoderDecoder(nn.Module):
 
     # hand-scheduled training pass
     def train_fwd(self, img, gt, seg_weight):
+        """returns (loss, (losses, logits, feats), saved); feats = the backbone's [(rows [B*N, C], h, w)] * 4"""
         B = img.shape[0]
         feats, sv_b = self.backbone.fwd(img)
         losses, logits, sv_h = self.decode_head.fwd_train(feats, B, gt, seg_weight)
-        return losses['loss_seg'], (losses, logits), (sv_b, sv_h, B)
+        return losses['loss_seg'], (losses, logits, feats), (sv_b, sv_h, B)
 
-    def train_bwd(self, saved, gscale):
+    def train_bwd(self, saved, gscale, img_grad_hook=None):
+        """img_grad_hook(d): called with the backbone's four output gradients before its backward pass starts; it may add into
+        them in place, or fill a None entry (uda.DACS: the ImageNet feature distance on stage 4)"""
         sv_b, sv_h, B = saved
         with ops.backward_scope():   # LayerNorm parameter gradients of the whole pass folded by one launch at the end
             dfs = self.decode_head.bwd_train(sv_h, B, gscale)
             rt.notify_grads_ready('decode_head', self.decode_head)
-            self.backbone.bwd(sv_b, [dfs.get(i) for i in range(4)])
+            d = [dfs.get(i) for i in range(4)]
+            if img_grad_hook is not None:
+                img_grad_hook(d)
+            self.backbone.bwd(sv_b, d)
         rt.join_lanes('wgrad')
 
     def forward_train(self, img, img_metas=None, gt_semantic_seg=None, seg_weight=None, return_feat=False):
         holder = {}
         loss = _TrainFn.apply(_Capture(self, holder), rt.anchor(img.device), (img, gt_semantic_seg, seg_weight))
-        losses, logits = holder['aux']
+        losses, logits, _ = holder['aux']
         out = add_prefix({'loss_seg': loss, 'acc_seg': losses['acc_seg']}, 'decode')
         return out, logits.permute(0, 3, 1, 2)
 
@@ -112,13 +144,10 @@ class EncoderDecoder(nn.Module):
         `rescale`, flipped back when the test pipeline flipped; per-image label maps (numpy) -- the reference's soft-max before
         the argmax is monotone and skipped."""
         seg_logit = self.encode_decode(img, img_meta)
-        meta = (img_meta[0] if isinstance(img_meta, (list, tuple)) else img_meta) or {}
-        if rescale and meta.get('ori_shape') is not None and tuple(meta['ori_shape'][:2]) != tuple(seg_logit.shape[2:]):
-            h, w = meta['ori_shape'][:2]
-            seg_logit = ops.upsample_logits_nchw(seg_logit.permute(0, 2, 3, 1).contiguous(), h, w)
-        if meta.get('flip'):
-            seg_logit = seg_logit.flip(dims=(3,) if meta['flip_direction'] == 'horizontal' else (2,))
-        return list(seg_logit.argmax(dim=1).cpu().numpy())
+        meta = _first_meta(img_meta)
+        if rescale and meta.get('ori_shape') is not None:
+            seg_logit = _resize_logits(seg_logit, meta['ori_shape'])
+        return _label_maps(_flip_back(seg_logit, meta))
 
 
 @SEGMENTORS.register_module()
@@ -146,29 +175,6 @@ class EventsEncoderDecoder(EncoderDecoder):
 
     def extract_feat(self, image, events=None):
         return self.backbone(self._image_only(image, events))
-
-    # hand-scheduled training pass (the same as EncoderDecoder's, plus the stage outputs and the image-gradient hook uda.DACS needs)
-    def train_fwd(self, img, gt, seg_weight):
-        """returns (loss, (losses, logits, feats), saved); feats = the backbone's [(rows [B*N, C], h, w)] * 4"""
-        B = img.shape[0]
-        feats, sv_b = self.backbone.fwd(img)
-        losses, logits, sv_h = self.decode_head.fwd_train(feats, B, gt, seg_weight)
-        return losses['loss_seg'], (losses, logits, feats), (sv_b, sv_h, B)
-
-    def train_bwd(self, saved, gscale, img_grad_hook=None):
-        """img_grad_hook(d): called with the backbone's four output gradients before its backward pass starts; it may add into
-        them in place, or fill a None entry (uda.DACS: the ImageNet feature distance on stage 4)"""
-        sv_b, sv_h, B = saved
-        with ops.backward_scope():
-            dfs = self.decode_head.bwd_train(sv_h, B, gscale)
-            if rt.grad_ready_hook is not None:
-                ops.gemm_flush_deferred()   # the head's queued weight gradients are final before they are reported
-            rt.notify_grads_ready('decode_head', self.decode_head)
-            d = [dfs.get(i) for i in range(4)]
-            if img_grad_hook is not None:
-                img_grad_hook(d)
-            self.backbone.bwd(sv_b, d)
-        rt.join_lanes('wgrad')
 
     def forward_train(self, image, events, gt_semantic_seg, seg_weight=None, return_feat=False):
         """encoder_decoder.py:446-482: (losses, seg_logits) -- seg_logits NCHW fp32 at 1/4 resolution"""
@@ -203,12 +209,8 @@ class EventsEncoderDecoder(EncoderDecoder):
             img = img[0]
         events = None if 'image' in kwargs else kwargs.get('events_vg')
         seg_logit = self.encode_decode(img, events)
-        meta = kwargs.get('img_metas')
-        if rescale and meta is not None:
-            meta = meta[0] if isinstance(meta, (list, tuple)) else meta
-            size = tuple(meta['ori_shape'][:2])
-            if size != tuple(seg_logit.shape[2:]):
-                seg_logit = ops.upsample_logits_nchw(seg_logit.permute(0, 2, 3, 1).contiguous(), size[0], size[1])
+        if rescale and kwargs.get('img_metas') is not None:
+            seg_logit = _resize_logits(seg_logit, _first_meta(kwargs['img_metas'])['ori_shape'])
         return seg_logit
 
     def inference(self, rescale, **kwargs):
@@ -217,16 +219,11 @@ class EventsEncoderDecoder(EncoderDecoder):
         if mode != 'whole':
             raise NotImplementedError(f"EventsEncoderDecoder: test_cfg.mode '{mode}' (only 'whole' is implemented)")
         output = torch.softmax(self.whole_inference(rescale, **kwargs), dim=1)
-        meta = kwargs.get('img_metas')
-        meta = (meta[0] if isinstance(meta, (list, tuple)) else meta) or {}
-        if meta.get('flip'):
-            assert meta['flip_direction'] in ('horizontal', 'vertical')
-            output = output.flip(dims=(3,) if meta['flip_direction'] == 'horizontal' else (2,))
-        return output
+        return _flip_back(output, _first_meta(kwargs.get('img_metas')))
 
     def simple_test(self, rescale=True, **kwargs):
         """:590-603: per-image label maps (numpy)"""
-        return list(self.inference(rescale, **kwargs).argmax(dim=1).cpu().numpy())
+        return _label_maps(self.inference(rescale, **kwargs))
 
 
 class _Capture:
@@ -534,25 +531,15 @@ class FusionEncoderDecoder(nn.Module):
         if self.train_type == 'cs2dz_image+raw-isr':
             test_cfg = {'output_type': 'fusion'} if test_cfg['output_type'] == 'image_isr' else {'output_type': 'image'}
         seg_logit = self.encode_decode(img, events, test_cfg=test_cfg)
-        meta = kwargs.get('img_metas')
-        if rescale and meta is not None:
-            meta = meta[0] if isinstance(meta, (list, tuple)) else meta
-            size = tuple(meta['ori_shape'][:2])
-            if size != tuple(seg_logit.shape[2:]):
-                seg_logit = ops.upsample_logits_nchw(seg_logit.permute(0, 2, 3, 1).contiguous(), size[0], size[1])
+        if rescale and kwargs.get('img_metas') is not None:
+            seg_logit = _resize_logits(seg_logit, _first_meta(kwargs['img_metas'])['ori_shape'])
         return seg_logit
 
     def inference(self, rescale, **kwargs):
         """encoder_decoder.py:938-971 (test_cfg.mode 'whole'): soft-max of the logits, flipped back when the test pipeline flipped"""
-        seg_logit = self.whole_inference(rescale, **kwargs)
-        output = torch.softmax(seg_logit, dim=1)
-        meta = kwargs.get('img_metas')
-        meta = (meta[0] if isinstance(meta, (list, tuple)) else meta) or {}
-        if meta.get('flip'):
-            assert meta['flip_direction'] in ('horizontal', 'vertical')
-            output = output.flip(dims=(3,) if meta['flip_direction'] == 'horizontal' else (2,))
-        return output
+        output = torch.softmax(self.whole_inference(rescale, **kwargs), dim=1)
+        return _flip_back(output, _first_meta(kwargs.get('img_metas')))
 
     def simple_test(self, rescale=True, **kwargs):
         """encoder_decoder.py:973-984: per-image label maps (numpy)"""
-        return list(self.inference(rescale, **kwargs).argmax(dim=1).cpu().numpy())
+        return _label_maps(self.inference(rescale, **kwargs))

@@ -20,6 +20,7 @@ no fusion; for 'cs2dz_image' optionally the frozen 3 -> 3 day -> night generator
 Out of scope here: the remaining train types ('cs2dz_image+d2n-isr', '_split', '_no-fusion'), OrgDACS,
 LightNet (cyclegan_light_path), the matplotlib debug panels, sky-mask / flare / cow-mask augmentations.
 """
+import contextlib
 import os
 import random
 from copy import deepcopy
@@ -55,9 +56,20 @@ def log_vars_to_float(log_vars):
     return {k: (v.item() if isinstance(v, torch.Tensor) else v) for k, v in log_vars.items()}
 
 
-def _null_ctx():
-    import contextlib
-    return contextlib.nullcontext()
+def _freeze(module):
+    """no gradients; runtime: the parameters' re-laid-out compute copies survive optimizer steps"""
+    for p in module.parameters():
+        p.requires_grad_(False)
+        p._cmda_frozen = True
+    return module
+
+
+def _frozen_generator(path, **kw):
+    """a CycleGAN generator in eval mode, frozen; `path` 'random' = seeded random init (no checkpoint exists offline; bench / tests)"""
+    g = define_G(**kw)
+    if path != 'random':
+        g.load_state_dict(torch.load(path, map_location='cpu'))
+    return _freeze(g.eval())
 
 
 # concurrency lanes of the captured iteration (DACS._capture; CMDA_GRAPH_LANES / DACS.graph_lane_set override): runtime.py documents them
@@ -105,27 +117,15 @@ class DACS(nn.Module):
         path = cfg.get('cyclegan_itrd2en_path', '')
         self.cyclegan_itrd2en = None
         if path and self.train_type in {'cs2dsec_image+events', 'cs2dsec_image+events_together'}:
-            self.cyclegan_itrd2en = define_G()
-            if path != 'random':  # 'random' = seeded random init (no checkpoint exists offline; bench / tests)
-                self.cyclegan_itrd2en.load_state_dict(torch.load(path, map_location='cpu'))
-            self.cyclegan_itrd2en.eval()
-            for p in self.cyclegan_itrd2en.parameters():
-                p.requires_grad_(False)
-                p._cmda_frozen = True   # runtime: its re-laid-out compute copies survive optimizer steps
+            self.cyclegan_itrd2en = _frozen_generator(path)
         self.cyclegan_id2in = None
         path = cfg.get('cyclegan_id2in_path', '')
         if path and self.train_type == 'cs2dz_image':
             # dacs.py:105-113, :368-372: the source image through a frozen 3 -> 3 generator, [-1, 1] in and out:
             # G((x * std + mean - 0.5) / 0.5) / 2 + 0.5 - mean) / std -- both maps folded into the generator's first / last layer
-            self.cyclegan_id2in = define_G(input_nc=3, output_nc=3)
-            if path != 'random':  # 'random' = seeded random init (no checkpoint exists offline; bench / tests)
-                self.cyclegan_id2in.load_state_dict(torch.load(path, map_location='cpu'))
+            self.cyclegan_id2in = _frozen_generator(path, input_nc=3, output_nc=3)
             mean, std = torch.tensor(self.IMNET_MEAN), torch.tensor(self.IMNET_STD)
             self.cyclegan_id2in.set_io_affine(2.0 * std, 2.0 * (mean - 0.5), 0.5 / std, (0.5 - mean) / std)
-            self.cyclegan_id2in.eval()
-            for p in self.cyclegan_id2in.parameters():
-                p.requires_grad_(False)
-                p._cmda_frozen = True
         if cfg.get('cyclegan_light_path', '') and self.train_type == 'cs2dz_image':
             # (dacs.py:115-123 loads a LightNet whose use is commented out, :373-377 and encoder_decoder.py:364-367)
             raise ValueError("cyclegan_light_path: LightNet is not implemented (the reference loads it but never applies it); "
@@ -134,20 +134,14 @@ class DACS(nn.Module):
         if self.enable_fdist and self.image_only:
             # dacs.py:234-241: for the image-only types a copy of the model config itself -- an EventsEncoderDecoder whose decode head is
             # built and never used; frozen as below
-            self.imnet_model = build_segmentor(deepcopy(cfg['model']))
-            for p in self.imnet_model.parameters():
-                p.requires_grad_(False)
-                p._cmda_frozen = True
+            self.imnet_model = _freeze(build_segmentor(deepcopy(cfg['model'])))
         elif self.enable_fdist:
             # dacs.py:234-242: an EncoderDecoder over the image backbone's config and the model's decode head (built, never used),
             # ImageNet weights from init_weights; frozen: no optimizer, no EMA, no gradient exchange sees it
             m = deepcopy(cfg['model'])
-            self.imnet_model = build_segmentor(dict(type='EncoderDecoder', backbone=m['backbone_image'], decode_head=m['decode_head'],
-                                                    pretrained=m.get('pretrained'), train_cfg=m.get('train_cfg'),
-                                                    test_cfg=m.get('test_cfg')))
-            for p in self.imnet_model.parameters():
-                p.requires_grad_(False)
-                p._cmda_frozen = True   # runtime: its re-laid-out compute copies survive optimizer steps
+            self.imnet_model = _freeze(build_segmentor(dict(type='EncoderDecoder', backbone=m['backbone_image'], decode_head=m['decode_head'],
+                                                            pretrained=m.get('pretrained'), train_cfg=m.get('train_cfg'),
+                                                            test_cfg=m.get('test_cfg'))))
         self.debug_fdist_mask = self.debug_gt_rescale = None
         assert cfg.get('sky_mask') is None, 'sky-mask augmentation is off in configs/fusion/* and not implemented'
         self.mixed_image_to_mixed_isr = bool(cfg.get('mixed_image_to_mixed_isr'))
@@ -168,8 +162,18 @@ class DACS(nn.Module):
         lfc = cfg.get('lambda_feature_consistency', -1)
         self.forward_cfg['lambda_feature_consistency'] = lfc if lfc != -1 else 0.25
         self._flat = None
+        self._opt = None                   # the FlatAdamW whose flat store the teacher shares (attach_flat_store)
         self._graph, self._graphs = None, {}
         self._graph_warmup = None
+        self._teacher_mode_set = False
+        # switches that bench.py, the tests and tools/ set from outside
+        self.fused_student_passes = True   # source + mixed samples as ONE student pass where the segmentor can (_iteration)
+        self.early_student = True          # the EARLY-STUDENT schedule of _iteration (needs lane 'T')
+        self.graph_lanes = True            # the captured iteration runs on concurrency lanes ...
+        self.graph_lane_set = None         # ... these (None: CMDA_LANES, else GRAPH_LANES)
+        self.final_pass_grad_hook = None   # runtime.grad_ready_hook during the step's last backward pass (data-parallel drivers)
+        self.inject_draws = None           # host decisions to use instead of _draw()'s
+        self.last_draws = self.last_mix = None   # what the last iteration drew / mixed
         for p in self.ema_model.parameters():
             p.requires_grad_(False)
 
@@ -441,6 +445,83 @@ class DACS(nn.Module):
             log_vars['src.loss_imnet_feat_dist'] = loss.view(())
         return hook
 
+    # -- the steps the fusion and the image-only iteration share -----------------------------------------------------------------
+    def _ext_wait(self):
+        """the stream lookup `rt.wait_external` takes when the optimizer update is overlapped (FlatAdamW.overlap), else None"""
+        opt = self._opt
+        return (lambda: getattr(opt, '_update_stream', None)) if (opt is not None and getattr(opt, 'overlap', False)) else None
+
+    def _teacher_mode(self):
+        if not self.ema_model.training or not self._teacher_mode_set:
+            self.ema_model.train()          # BatchNorm keeps batch statistics (and updates its running stats) ...
+            set_stochastic(self.ema_model, False)  # ... but DropPath / Dropout2d are off in the teacher (dacs.py:458-462)
+            self._teacher_mode_set = True
+
+    def _mix_targets(self, logits, lab, classes):
+        """the teacher's 1/4-resolution logits -> pseudo-labels -> ClassMix'd labels / weights (dacs.py:653-711, :716-771 for the targets)"""
+        B, H, W = lab.shape
+        pseudo_label, _, count = ops.pseudo_label(logits, H, W, self.pseudo_threshold, want_prob=False)
+        pseudo_weight = ops.pseudo_weight(count, B, H, W, self.psweight_ignore_top, self.psweight_ignore_bottom)
+        gt_pixel_weight = torch.ones(B, H, W, dtype=torch.float32, device=lab.device)
+        mixed_lbl = ops.class_mix_label(lab, pseudo_label, lab, classes).view(B, 1, H, W)
+        mixed_weight = ops.class_mix(gt_pixel_weight.view(B, 1, H, W), pseudo_weight.view(B, 1, H, W), lab, classes).view(B, H, W)
+        return pseudo_label, count, mixed_lbl, mixed_weight
+
+    def _mixed_image(self, day_image, night_image, lab, classes, ctl):
+        """ClassMix + strong augmentation (dacs.py:716-724; dacs_transforms.py:64-98, kornia semantics): the on/off gates and the
+        per-sample parameters are read from the control block by the kernels"""
+        mixed_img = ops.class_mix(day_image, night_image, lab, classes)
+        if self.color_jitter_p < 1.0:
+            ops.color_jitter_(mixed_img, ctl['jitter'], ctl['jitter_on'])
+        if self.blur:
+            ops.gaussian_blur_(mixed_img, ctl['taps_x'], ctl['taps_y'], ctl['blur_on'])
+        return mixed_img
+
+    @contextlib.contextmanager
+    def _last_backward(self, dev):
+        """around the step's LAST backward pass: gradients it reports final are final for the step, so a data-parallel driver may start
+        their all-reduce underneath the rest of the pass (`final_pass_grad_hook` armed as runtime.grad_ready_hook, restored on exit)"""
+        hook = self.final_pass_grad_hook
+        if hook is not None and dev.type == 'cuda' and torch.cuda.is_current_stream_capturing() and rt._conc['seg'] is None:
+            hook = None   # one monolithic capture cannot call out; the segmented capture records the hook as a host step
+        prev = rt.grad_ready_hook
+        try:
+            if hook is not None:
+                rt.grad_ready_hook = hook
+            yield
+        finally:
+            rt.grad_ready_hook = prev
+
+    def _two_passes(self, student, fwd_src, fwd_mix, keep_mix, rows4, fd, join_fd, one, log_vars):
+        """the student's source and mixed step as two passes (the image-only types, and the fusion routes the joint pass does not
+        cover): the mixed forward runs after the source forward (BatchNorm running statistics), on lane 'T' next to the source
+        backward; the mixed backward follows the join (gradients accumulate).  fwd_src / fwd_mix: the argument tuples of
+        `student.train_fwd`; keep_mix: what lane 'T' keeps alive for the mixed forward; rows4(saved, feats) -> the source pass's stage-4
+        image rows (feature distance); join_fd: the feature-distance targets were made on lane 'T', which this route otherwise joins
+        only behind the source backward."""
+        loss, (losses, _, feats_src), saved_src = student.train_fwd(*fwd_src)
+        log_vars['decode.loss_seg'], log_vars['decode.acc_seg'] = loss, losses['acc_seg']
+        with rt.lane('T', *keep_mix):
+            loss, (losses, _, _), saved_mix = student.train_fwd(*fwd_mix)
+        log_vars['mix.decode.loss_seg'], log_vars['mix.decode.acc_seg'] = loss, losses['acc_seg']
+        log_vars['loss'] = loss   # _parse_losses of the mixed step overwrites 'loss' (dacs.py:851-857)
+        fd_hook = None
+        if fd is not None:
+            if join_fd:
+                rt.join_lanes('T')
+            fd_hook = self._fdist_hook(fd, lambda: rows4(saved_src, feats_src), one, log_vars)
+        student.train_bwd(saved_src, one, img_grad_hook=fd_hook)
+        del saved_src, feats_src
+        rt.join_lanes('T')
+        with self._last_backward(one.device):
+            student.train_bwd(saved_mix, one)
+
+    @staticmethod
+    def _with_fdist(extras, fd):
+        if fd is not None:
+            extras.update(fdist_feat_imnet=fd['ft'], fdist_mask=fd['mask'], fdist_gt_rescale=fd['rescaled'], fdist_count=fd['count'])
+        return extras
+
     # -- the device work of one iteration: no host reads, no host-dependent launch shapes (capturable: hipGraph segments) ----------
     def _iteration(self, src, tgt, ctl, use_events, teacher_second, direction):
         """dacs.py:397-860 minus the host decisions (`_draw`), the EMA update and the optimizer step.  `ctl` = device views of
@@ -449,8 +530,7 @@ class DACS(nn.Module):
         if self.image_only:
             return self._iteration_image(src, tgt, ctl)
         tt = self.train_type
-        opt = getattr(self, '_opt', None)
-        ext_wait = (lambda: getattr(opt, '_update_stream', None)) if (opt is not None and getattr(opt, 'overlap', False)) else None
+        ext_wait = self._ext_wait()
         day_image, day_isr, day_label = src['image'], src['img_self_res'], src['label']
         day_events = night_events = None
         if tt == 'cs2dz_image+raw-isr':
@@ -460,10 +540,7 @@ class DACS(nn.Module):
         B, _, H, W = day_image.shape
         dev = day_image.device
         log_vars = {}
-        if not self.ema_model.training or not getattr(self, '_teacher_mode_set', False):
-            self.ema_model.train()          # BatchNorm keeps batch statistics (and updates its running stats) ...
-            set_stochastic(self.ema_model, False)  # ... but DropPath / Dropout2d are off in the teacher (dacs.py:458-462)
-            self._teacher_mode_set = True
+        self._teacher_mode()
         student, teacher = self.get_model(), self.get_ema_model()
         cfg_s = self._cfg_student(use_events)
         one = rt.ones1(dev)
@@ -484,21 +561,11 @@ class DACS(nn.Module):
                 ema = teacher.encode_decode_lowres(night_image, teacher_second, test_cfg=dict(self.forward_cfg, fusion_isr=True))
             else:
                 ema = teacher.encode_decode_lowres(night_image, teacher_second, test_cfg=self.forward_cfg)
-            pseudo_label, _, count = ops.pseudo_label(ema['fusion_output'], H, W, self.pseudo_threshold, want_prob=False)
-            pseudo_weight = ops.pseudo_weight(count, B, H, W, self.psweight_ignore_top, self.psweight_ignore_bottom)
-            gt_pixel_weight = torch.ones(B, H, W, dtype=torch.float32, device=dev)
-            mixed_lbl = ops.class_mix_label(lab, pseudo_label, lab, classes).view(B, 1, H, W)
-            mixed_weight = ops.class_mix(gt_pixel_weight.view(B, 1, H, W), pseudo_weight.view(B, 1, H, W), lab, classes).view(B, H, W)
-            return ema, pseudo_label, count, mixed_lbl, mixed_weight
+            return (ema,) + self._mix_targets(ema['fusion_output'], lab, classes)
 
         def mixed_inputs():
-            """ClassMix + strong augmentation + ISR of the mixed image (dacs.py:716-771; dacs_transforms.py:64-98, kornia
-            semantics): the on/off gates and the per-sample parameters are read from the control block by the kernels"""
-            mixed_img = ops.class_mix(day_image, night_image, lab, classes)
-            if self.color_jitter_p < 1.0:
-                ops.color_jitter_(mixed_img, ctl['jitter'], ctl['jitter_on'])
-            if self.blur:
-                ops.gaussian_blur_(mixed_img, ctl['taps_x'], ctl['taps_y'], ctl['blur_on'])
+            """the mixed image and its ISR (dacs.py:716-771)"""
+            mixed_img = self._mixed_image(day_image, night_image, lab, classes, ctl)
             gray = ops.isr_gray(mixed_img)
             mixed_isr = ops.isr_from_gray(gray, self.isr_parms['val_range'], self.isr_parms['_threshold'],
                                           self.isr_parms['_clip_range'], self.isr_parms['shift_pixel'], direction, dirs_dev=ctl['dirs'])
@@ -510,8 +577,8 @@ class DACS(nn.Module):
         # on this lane at once, the generator on the side lane, and the student's encoders start as soon as the generator is done; lane
         # 'T' is joined in front of the decode head's loss (train_fwd_passes before_head).  The reference's order (teacher before the
         # mixed step, dacs.py:653-860) only matters through these data dependencies.
-        early = (getattr(self, 'early_student', True) and rt.lane_enabled('T') and getattr(self, 'fused_student_passes', True)
-                 and hasattr(student, 'train_fwd_passes'))
+        fused = self.fused_student_passes and hasattr(student, 'train_fwd_passes')
+        early = self.early_student and rt.lane_enabled('T') and fused
         # OVERLAPPED UPDATE (FlatAdamW.overlap): AdamW, the gradient clear and the EMA update of the step boundary run on the optimizer's
         # own stream; the part of the iteration that reads no trainable weight -- the mixed inputs and the frozen generator -- is enqueued
         # FIRST and runs underneath them, then this lane waits for that stream (`wait_external`), refreshes the weight copies and goes on.
@@ -574,13 +641,8 @@ class DACS(nn.Module):
         else:
             in_src = {'image': day_image, 'events': day_events if use_events else day_isr}
             in_mix = {'image': mixed_img, 'events': mixed_events if use_events else mixed_isr}
-        hook = getattr(self, 'final_pass_grad_hook', None)
-        if hook is not None and dev.type == 'cuda' and torch.cuda.is_current_stream_capturing() and rt._conc['seg'] is None:
-            hook = None   # one monolithic capture cannot call out; the segmented capture records the hook as a host step
-        prev_hook = rt.grad_ready_hook
 
-        if (getattr(self, 'fused_student_passes', True) and hasattr(student, 'train_fwd_passes')
-                and student._joint_ok(in_src['image'], in_src['events'], cfg_s)):
+        if fused and student._joint_ok(in_src['image'], in_src['events'], cfg_s):
             # ONE student pass over the source and the mixed samples: both steps run the same weights (the optimizer steps after
             # both, dacs.py:523 / :860 only accumulate gradients), so the 2B samples travel as one batch -- half the launches,
             # twice the rows per GEMM.  What is per step in the reference stays per step: BatchNorm batch statistics and the order
@@ -595,68 +657,34 @@ class DACS(nn.Module):
             log_vars['decode.loss_seg'], log_vars['decode.acc_seg'] = l_src, d_src['acc_seg']
             log_vars['mix.decode.loss_seg'], log_vars['mix.decode.acc_seg'] = l_mix, d_mix['acc_seg']
             log_vars['loss'] = l_mix   # _parse_losses of the mixed step overwrites 'loss' (dacs.py:851-857)
-            # the only backward pass of the iteration: gradients it reports final are final for the step, so a data-parallel
-            # driver may start their all-reduce underneath the rest of the pass (runtime.grad_ready_hook)
-            if hook is not None:
-                rt.grad_ready_hook = hook
-            try:
+            with self._last_backward(dev):   # the only backward pass of the iteration
                 student.train_bwd(saved, one, img_grad_hook=fd_hook)
-            finally:
-                rt.grad_ready_hook = prev_hook
             del saved
         else:
-            # two passes (routes the joint pass does not cover): the mixed forward runs after the source forward (BatchNorm
-            # running statistics), next to the source backward; the mixed backward follows the join (gradients accumulate)
-            loss, (losses, _, feats_src), saved_src = student.train_fwd(in_src, day_label, None, cfg_s)
-            log_vars['decode.loss_seg'], log_vars['decode.acc_seg'], log_vars['loss'] = loss, losses['acc_seg'], loss
-            with rt.lane('T'):
-                loss, (losses, _, _), saved_mix = student.train_fwd(in_mix, mixed_lbl, mixed_weight, cfg_s)
-            log_vars['mix.decode.loss_seg'], log_vars['mix.decode.acc_seg'] = loss, losses['acc_seg']
-            log_vars['loss'] = loss   # _parse_losses of the mixed step overwrites 'loss' (dacs.py:851-857)
-            fd_hook = None
-            if fd is not None:
-                if early:   # (the frozen encoder ran on lane 'T', which this route joins only behind the source backward)
-                    rt.join_lanes('T')
-                # the source pass's stage-4 image rows: the joint buffer's block 0, or the image encoder's own output
-                rows4 = (lambda: feats_src[3][0]) if saved_src[0] == 'joint' else (lambda: feats_src['f_image'][3][0])
-                fd_hook = self._fdist_hook(fd, rows4, one, log_vars)
-            student.train_bwd(saved_src, one, img_grad_hook=fd_hook)
-            del saved_src, feats_src
-            rt.join_lanes('T')
-            if hook is not None:   # the second (last) backward pass: see above
-                rt.grad_ready_hook = hook
-            try:
-                student.train_bwd(saved_mix, one)
-            finally:
-                rt.grad_ready_hook = prev_hook
-            del saved_mix
+            # the source pass's stage-4 image rows: the joint buffer's block 0, or the image encoder's own output; under EARLY-STUDENT
+            # the frozen encoder ran on lane 'T'
+            self._two_passes(student, (in_src, day_label, None, cfg_s), (in_mix, mixed_lbl, mixed_weight, cfg_s), (),
+                             lambda saved, feats: feats[3][0] if saved[0] == 'joint' else feats['f_image'][3][0],
+                             fd, early, one, log_vars)
         extras = dict(mixed_img=mixed_img, mixed_lbl=mixed_lbl, mixed_isr=mixed_isr, pseudo_weight=mixed_weight,
                       pseudo_label=pseudo_label, classes=classes, mixed_events=mixed_events, day_events=day_events,
                       teacher_logits=ema, pseudo_count=count)
-        if fd is not None:
-            extras.update(fdist_feat_imnet=fd['ft'], fdist_mask=fd['mask'], fdist_gt_rescale=fd['rescaled'], fdist_count=fd['count'])
-        return log_vars, extras
+        return log_vars, self._with_fdist(extras, fd)
 
     def _iteration_image(self, src, tgt, ctl):
         """the image-only iteration ('cs2dsec_image' / 'cs2dz_image'; dacs.py:363-377, :467-468, :569-570, :597-600, :701-791): the
-        same host / device split and the same step boundary as `_iteration`.  Schedule: the frozen generator (cs2dz_image) first -- it
-        reads no trainable weight, so it runs underneath an overlapped optimizer update; then the teacher, its pseudo-labels / weights
-        and the feature-distance targets on lane 'T' beside the mixed image on this lane; the student's source pass here, its mixed
-        pass on lane 'T' beside the source backward (BatchNorm running statistics: source first, as in the reference); the mixed
-        backward after the join (the gradients add up)."""
-        opt = getattr(self, '_opt', None)
-        ext_wait = (lambda: getattr(opt, '_update_stream', None)) if (opt is not None and getattr(opt, 'overlap', False)) else None
+        same host / device split, the same step boundary and the same shared steps as `_iteration`.  Schedule: the frozen generator
+        (cs2dz_image) first -- it reads no trainable weight, so it runs underneath an overlapped optimizer update; then the teacher,
+        its pseudo-labels / weights and the feature-distance targets on lane 'T' beside the mixed image on this lane; then the
+        student's two passes (`_two_passes`)."""
+        ext_wait = self._ext_wait()
         day_image, day_label = src['image'], src['label']
         night_image = tgt['warp_image'] if 'warp_image' in tgt else tgt['image']
         B, _, H, W = day_image.shape
-        dev = day_image.device
         log_vars = {}
-        if not self.ema_model.training or not getattr(self, '_teacher_mode_set', False):
-            self.ema_model.train()          # BatchNorm keeps batch statistics (and updates its running stats) ...
-            set_stochastic(self.ema_model, False)  # ... but DropPath / Dropout2d are off in the teacher (dacs.py:458-462)
-            self._teacher_mode_set = True
+        self._teacher_mode()
         student, teacher = self.get_model(), self.get_ema_model()
-        one = rt.ones1(dev)
+        one = rt.ones1(day_image.device)
         lab = day_label.view(B, H, W)
         classes = ctl['classes']
         if self.cyclegan_id2in is not None:
@@ -670,46 +698,14 @@ class DACS(nn.Module):
             if self.enable_fdist:
                 fd = self._fdist_targets(day_image, day_label)
             ema = teacher.encode_decode_lowres(night_image)
-            pseudo_label, _, count = ops.pseudo_label(ema, H, W, self.pseudo_threshold, want_prob=False)
-            pseudo_weight = ops.pseudo_weight(count, B, H, W, self.psweight_ignore_top, self.psweight_ignore_bottom)
-            gt_pixel_weight = torch.ones(B, H, W, dtype=torch.float32, device=dev)
-            mixed_lbl = ops.class_mix_label(lab, pseudo_label, lab, classes).view(B, 1, H, W)
-            mixed_weight = ops.class_mix(gt_pixel_weight.view(B, 1, H, W), pseudo_weight.view(B, 1, H, W), lab, classes).view(B, H, W)
-        # ClassMix + strong augmentation of the mixed image (dacs.py:719-724): gates and parameters from the control block
-        mixed_img = ops.class_mix(day_image, night_image, lab, classes)
-        if self.color_jitter_p < 1.0:
-            ops.color_jitter_(mixed_img, ctl['jitter'], ctl['jitter_on'])
-        if self.blur:
-            ops.gaussian_blur_(mixed_img, ctl['taps_x'], ctl['taps_y'], ctl['blur_on'])
-        hook = getattr(self, 'final_pass_grad_hook', None)
-        if hook is not None and dev.type == 'cuda' and torch.cuda.is_current_stream_capturing() and rt._conc['seg'] is None:
-            hook = None   # one monolithic capture cannot call out; the segmented capture records the hook as a host step
-        prev_hook = rt.grad_ready_hook
-        loss, (losses, _, feats_src), saved_src = student.train_fwd(day_image, day_label, None)
-        log_vars['decode.loss_seg'], log_vars['decode.acc_seg'] = loss, losses['acc_seg']
-        with rt.lane('T', mixed_img):
-            loss, (losses, _, _), saved_mix = student.train_fwd(mixed_img, mixed_lbl, mixed_weight)
-        log_vars['mix.decode.loss_seg'], log_vars['mix.decode.acc_seg'] = loss, losses['acc_seg']
-        log_vars['loss'] = loss   # _parse_losses of the mixed step overwrites 'loss' (dacs.py:851-857)
-        fd_hook = None
-        if fd is not None:
-            rt.join_lanes('T')   # (the frozen encoder ran on lane 'T')
-            fd_hook = self._fdist_hook(fd, lambda: feats_src[3][0], one, log_vars)
-        student.train_bwd(saved_src, one, img_grad_hook=fd_hook)
-        del saved_src, feats_src
-        rt.join_lanes('T')
-        if hook is not None:   # the last backward pass: its gradients are final for the step (runtime.grad_ready_hook)
-            rt.grad_ready_hook = hook
-        try:
-            student.train_bwd(saved_mix, one)
-        finally:
-            rt.grad_ready_hook = prev_hook
-        del saved_mix
+            pseudo_label, count, mixed_lbl, mixed_weight = self._mix_targets(ema, lab, classes)
+        mixed_img = self._mixed_image(day_image, night_image, lab, classes, ctl)
+        # (the frozen encoder ran on lane 'T': joined before the source backward when the feature distance is on)
+        self._two_passes(student, (day_image, day_label, None), (mixed_img, mixed_lbl, mixed_weight), (mixed_img,),
+                         lambda saved, feats: feats[3][0], fd, True, one, log_vars)
         extras = dict(mixed_img=mixed_img, mixed_lbl=mixed_lbl, pseudo_weight=mixed_weight, pseudo_label=pseudo_label, classes=classes,
                       teacher_logits=ema, pseudo_count=count, day_image=day_image)
-        if fd is not None:
-            extras.update(fdist_feat_imnet=fd['ft'], fdist_mask=fd['mask'], fdist_gt_rescale=fd['rescaled'], fdist_count=fd['count'])
-        return log_vars, extras
+        return log_vars, self._with_fdist(extras, fd)
 
     # -- hipGraph replay of the iteration ------------------------------------------------------------------------------------------
     def enable_graph(self, warmup_iters=2):
@@ -733,7 +729,7 @@ class DACS(nn.Module):
         deferred.prealloc(dev, ws_lanes)
         torch.cuda.synchronize(dev)
         rt.refresh(force=True)   # every copy exists and is current before the capture starts
-        lanes = getattr(self, 'graph_lane_set', None)
+        lanes = self.graph_lane_set
         if lanes is None and os.environ.get('CMDA_LANES'):   # tuning: comma-separated lane set (runtime.set_concurrency)
             lanes = set(os.environ['CMDA_LANES'].split(','))
         if lanes is None:
@@ -753,7 +749,7 @@ class DACS(nn.Module):
         import gc
         gc.collect()
         torch.cuda.empty_cache()
-        rt.set_concurrency(bool(getattr(self, 'graph_lanes', True)), lanes, seg=seg)
+        rt.set_concurrency(bool(self.graph_lanes), lanes, seg=seg)
         try:
             seg.begin(seg.main)
             out = self._iteration(st_src, st_tgt, cb['d'], use_events_struct, second, direction)
@@ -773,21 +769,21 @@ class DACS(nn.Module):
         day_label = src['label']
         B, _, H, W = src['image'].shape
         dev = src['image'].device
-        draws = getattr(self, 'inject_draws', None) or self._draw(day_label, H, W)
+        draws = self.inject_draws or self._draw(day_label, H, W)
         self.last_draws = draws
         if not self.image_only:
             self.forward_cfg['isr_events_fusion_choice'] = draws['choice']
         use_events = not self.image_only and tt != 'cs2dz_image+raw-isr' and draws['choice'] > self.random_choice_thres
         cb = self._control_block(dev, B, H, W)
         self._stage(cb, draws)
-        opt = getattr(self, '_opt', None)
+        opt = self._opt
 
         def boundary():
             """the step boundary's device work that precedes this iteration: the (possibly postponed) optimizer update, then the EMA
             teacher update -- with an overlapped update both on the optimizer's stream"""
             if opt is not None:
                 opt.flush()
-            with (opt._on_update_stream() if opt is not None else _null_ctx()):
+            with (opt._on_update_stream() if opt is not None else contextlib.nullcontext()):
                 if self.local_iter == 0:
                     self._init_ema_weights()
                 if self.local_iter > 0:
@@ -806,8 +802,6 @@ class DACS(nn.Module):
                     and self.local_iter >= self._graph_warmup)
         if graph_on:
             key = (struct_events, ndir_key, tuple(src['image'].shape), tuple(tgt_shape(tgt)))
-            if not hasattr(self, '_graphs'):
-                self._graphs = {}
             if key not in self._graphs:
                 # (first replay, another launch structure, or another batch shape: the captured launches are shape-specific)
                 boundary()
