@@ -500,3 +500,516 @@ def test_rows_fill_cast_pad_nchw_pad(tgt):
         want = torch.zeros(2, 7, 9, 8)
         want[..., :3] = img.permute(0, 2, 3, 1)
         assert torch.equal(dst.cpu().float(), want.view(-1, 8).to(dt).float())
+
+
+# ------------------------------------------------------------------ BatchNorm family (csrc/batchnorm.hip) against float64
+# The checker is float64 torch written out here, on the stored inputs (bf16 values widened): mean, biased variance, eps inside the
+# square root, unbiased variance for running_var, the momentum blend applied group by group in `order`.
+_BN_ORDER = {1: None, 2: (1, 0), 3: (2, 0, 1), 4: (2, 0, 3, 1), 8: (5, 2, 7, 0, 3, 6, 1, 4)}
+
+
+def _bn_rows_per_block(rows_total, C):
+    """rows_per_block / rows_per_block_apply of batchnorm.hip restated: halve from 512 / 256 while the grid stays under 1024 / 2048
+    blocks, down to 32 / 16 (rows_total = rows per group x groups, gx = channel blocks of 256)"""
+    gx = (C // 4 + 63) // 64
+    red, app = 512, 256
+    while red > 32 and -(-rows_total // red) * gx < 1024:
+        red >>= 1
+    while app > 16 and -(-rows_total // app) * gx < 2048:
+        app >>= 1
+    return red, app
+
+
+def _bn_inputs(M, C, G, dt, seed):
+    """x ~ N(3 + 7 g, 2^2) in group g (the inputs of test_batchnorm; the group means lie 3.5 standard deviations apart, so another
+    group's mean / rstd is visibly wrong), gamma in [0.5, 1.5], beta ~ 0.2 N(0, 1)"""
+    gen = torch.Generator().manual_seed(seed)
+    x = torch.randn(G, M, C, generator=gen) * 2 + 3
+    x += 7.0 * torch.arange(G, dtype=torch.float32).view(G, 1, 1)
+    return x.to(dt), torch.rand(C, generator=gen) + 0.5, torch.randn(C, generator=gen) * 0.2, gen
+
+
+def _bn_ref64(x, g, b, eps):
+    """x [G, M, C] stored values -> float64 mean, biased variance, rstd [G, C], xhat and the pre-activation [G, M, C]"""
+    x64 = x.double()
+    mean = x64.mean(1)
+    var = ((x64 - mean[:, None]) ** 2).mean(1)
+    rstd = (var + eps).rsqrt()
+    xhat = x64.sub_(mean[:, None]).mul_(rstd[:, None])
+    return mean, var, rstd, xhat, xhat * g.double() + b.double()
+
+
+def _bn_train_case(tgt, dt, tol, relu, M, C, G, ld, coff, seed):
+    eps, mom = 1e-5, 0.1
+    order = _BN_ORDER[G]
+    x, g, b, gen = _bn_inputs(M, C, G, dt, seed)
+    rm0, rv0 = torch.randn(C, generator=gen), torch.rand(C, generator=gen) + 0.5
+    dg0, db0 = torch.randn(C, generator=gen), torch.randn(C, generator=gen)
+    mean, var, rstd, xhat, pre = _bn_ref64(x, g, b, eps)
+    shift = x[:, 0].double()
+    dy = torch.randn(G * M, ld, generator=gen).to(dt)
+    dys = dy.view(G, M, ld)[:, :, coff:coff + C]
+    band = None
+    if relu:
+        # The gradient of an element whose pre-activation is within rounding of zero is arbitrary, and it is the element's WHOLE
+        # gradient.  Exactly the elements whose float64 pre-activation lies within 1e-4 of zero are left out of the dx comparison (at
+        # most 1e-3 of a case, asserted on the reference alone); everything else is compared with no allowance.  dy is zero on those
+        # elements, so a mask the kernel's own statistics (1e-6 off) flip there moves neither dgamma / dbeta nor the dx of the other
+        # elements: those keep their plain bounds at every size (at 4 x 32768 x 1024 a handful of flips per case is expected, each
+        # worth |dy| ~ 1 against a dbeta bound of 0.1).
+        band = pre.abs() < 1e-4
+        check_le('bn relu: share of elements within 1e-4 of the mask edge', band.double().mean().item(), 1e-3)
+        dys.masked_fill_(band, 0)
+    dy64 = dys.double()
+    if relu:
+        dy64 = dy64 * (pre > 0)
+    yref = pre.clamp_(min=0) if relu else pre
+    s1, s2 = dy64.sum(1), (dy64 * xhat).sum(1)
+    dxref = (dy64 - s1[:, None] / M - xhat.mul_(s2[:, None] / M)).mul_((g.double() * rstd)[:, None])
+    # running statistics: the float64 recurrence, group after group in `order`.  M = 1: bn_finalize_kernel skips the unbiased factor
+    # M / (M - 1) (torch raises there; the contract of the kernel is running_var <- blend with the biased variance, 0)
+    rm, rv = rm0.double(), rv0.double()
+    for i in (order or range(G)):
+        rm = (1 - mom) * rm + mom * mean[i]
+        rv = (1 - mom) * rv + mom * (var[i] * M / (M - 1) if M > 1 else var[i])
+    xd, gd, bd, rmd, rvd = map(tgt.to, (x.view(G * M, C), g, b, rm0.clone(), rv0.clone()))
+    y = torch.zeros(G * M, ld, dtype=dt, device=tgt.device)
+    mean_k, rstd_k = ops.bn_train_fwd(xd, gd, bd, y, rmd, rvd, M, C, eps, mom, relu, ld, coff, groups=G, order=order)
+    assert_close(y[:, coff:coff + C], yref.view(G * M, C), tol, name='bn fwd')
+    assert not y[:, :coff].any().item() and not y[:, coff + C:].any().item(), 'columns outside the slice were written'
+    assert_close(mean_k, mean, 1e-5, name='bn saved mean')
+    if M > 1:
+        # 1e-5 (the project's bound for the statistics of well-conditioned input, relative here to each channel's own rstd) plus the
+        # channel's conditioning term: the variance is taken in one pass around row 0 of the group, its relative error is at most
+        # K 2^-24 kappa (test_batchnorm_conditioning) and rstd's half that.  kappa reaches ~20 here (row 0 up to 4.4 sigma off its
+        # channel's mean): a plain 1e-5 of max rstd was within 1.5x at 4 x 32768 x 1024 on an MI355X (6.7e-6), and the conditioning
+        # term alone, measured at 4096 rows, within 1.2x at 600000 rows on the emulator (longer fp32 sums: 8.6 x 2^-24 kappa).
+        # Wrong statistics (another group's, a lost row block) are off by orders of magnitude more.
+        kappa = 1 + (mean - shift) ** 2 / var
+        bound = 1e-5 + _BN_COND_K / 2 * 2.0 ** -24 * kappa
+        check_le('bn saved rstd: relative error / (1e-5 + K/2 2^-24 kappa)', ((rstd_k.double().cpu() - rstd).abs() / rstd / bound).max().item(), 1.0)
+    else:
+        assert_close(rstd_k, rstd, 1e-5, name='bn saved rstd')   # (one row: variance 0 exactly, rstd = eps^-1/2)
+    assert_close(rmd, rm, 1e-5, name='running_mean')
+    assert_close(rvd, rv, 1e-5, name='running_var')
+    dg, db = tgt.to(dg0.clone()), tgt.to(db0.clone())   # (the kernels add into dgamma / dbeta)
+    dx = ops.bn_train_bwd(tgt.to(dy), xd, mean_k, rstd_k, gd, bd, dg, db, M, C, relu, ld, coff, groups=G)
+    dx, dxref = dx.float().cpu().view(G, M, C), dxref
+    if relu:
+        dx, dxref = dx[~band], dxref[~band]
+    if M > 2:
+        assert_close(dx, dxref, tol, name='bn dx')
+    else:
+        # one row: dx = 0; two rows: xhat = +-1 and dx cancels to O(eps / var) of its terms (max |dx| 2e-4 here), so the fp32 rounding
+        # of the terms is not small against max |dx|.  The bound is taken relative to the terms' size max |gamma rstd dy| -- what
+        # max |dx| is in every other case
+        assert_close(dx, dxref, 0, atol=tol * ((g.double() * rstd).abs().max() * dy64.abs().max()).item(), name='bn dx (M <= 2)')
+    assert_close(dg, dg0.double() + s2.sum(0), 1e-4, name='bn dgamma')
+    assert_close(db, db0.double() + s1.sum(0), 1e-4, name='bn dbeta')
+
+
+# (rows per group M, C, groups).  Edges: M = 1 / 2, fewer rows than the 4-row unroll x 4 row lanes, ragged tails, C over several
+# 256-channel blocks and not a multiple of 256.  Then one case per rows_per_block pair (reduce / apply), recomputed from the heuristics
+# with rows = M x groups and gx = 1 (C <= 256): every one has more than 32 row blocks PER GROUP, so the 32 workspace slots wrap
+#   (600000, 4, 1): ceil(600000 / 512) = 1172 >= 1024 -> 512;  ceil(600000 / 256) = 2344 >= 2048 -> 256      1172 blocks per group
+#   (37500, 4, 8):  300000 / 512 = 586, / 256 = 1172 -> 256;   / 256 = 1172, / 128 = 2344 -> 128              147 blocks per group
+#   (150000, 4, 1): 293, 586, / 128 = 1172 -> 128;             586, 1172, / 64 = 2344 -> 64                   1172 blocks per group
+#   (35000, 4, 2):  70000: 137, 274, 547, / 64 = 1094 -> 64;   274, 547, 1094, / 32 = 2188 -> 32              547 blocks per group
+#   (20000, 256, 1): 40, 79, 157, 313 -> floor 32;             79, 157, 313, 625 -> floor 16                  625 blocks per group
+# (the head shapes of test_batchnorm_head_shapes: 4 x 32768 rows, C = 256 -> 128 / 64; C = 1024, gx = 4 -> 512 / 256)
+_BN_EDGES = [(1, 8, 1), (2, 8, 1), (5, 4, 1), (37, 260, 1), (4099, 260, 1), (1000, 516, 3), (515, 1028, 2)]
+_BN_RPB = {(600000, 4, 1): (512, 256), (37500, 4, 8): (256, 128), (150000, 4, 1): (128, 64), (35000, 4, 2): (64, 32),
+           (20000, 256, 1): (32, 16)}
+
+
+@pytest.mark.parametrize('dt,tol', DT)
+@pytest.mark.parametrize('relu', [True, False])
+@pytest.mark.parametrize('M,C,G', _BN_EDGES + list(_BN_RPB))
+def test_batchnorm_shapes(tgt, dt, tol, relu, M, C, G):
+    """cmda_bn_train_fwd + cmda_bn_train_bwd against float64 at the shapes where the kernels' indexing can go wrong: y inside its
+    column slice and zeros outside, saved mean / rstd per group, the running statistics after a grouped call (from non-trivial
+    starting values, groups applied in `order`), dx, dgamma / dbeta accumulated onto non-zero starting values.
+    M = 1 follows bn_finalize_kernel: the unbiased factor is skipped."""
+    if (M, C, G) in _BN_RPB:
+        assert _bn_rows_per_block(M * G, C) == _BN_RPB[(M, C, G)] and M > 32 * _BN_RPB[(M, C, G)][0]
+    _bn_train_case(tgt, dt, tol, relu, M, C, G, ld=C + 12, coff=8, seed=M + C + G)
+
+
+@pytest.mark.parametrize('dt,tol', DT)
+@pytest.mark.parametrize('relu', [True, False])
+@pytest.mark.parametrize('C,ld,coff', [(256, 1024, 0), (256, 1024, 256), (256, 1024, 768), (1024, 1024, 0)])
+@pytest.mark.parametrize('rows', [2048, 32768])
+def test_batchnorm_head_shapes(tgt, dt, tol, relu, C, ld, coff, rows):
+    """the decode head's calls: a 256-channel slice of the 1024-channel ASPP concat buffer (ldy = lddy = 1024) and the depthwise
+    branch's 1024 channels, four groups (image / events / fusion / ISR features through the shared decoder) with their running
+    statistics applied in the order (2, 0, 3, 1); 2 x 128 x 128 rows per group as in training, 2048 on the emulator too"""
+    if rows > 2048 and tgt.device.type != 'cuda':
+        pytest.skip('the full 2 x 128 x 128 rows per group: GPU only (emulator run time)')
+    if rows == 32768:
+        assert _bn_rows_per_block(4 * rows, C) == ((128, 64) if C == 256 else (512, 256))
+    _bn_train_case(tgt, dt, tol, relu, rows, C, 4, ld=ld, coff=coff, seed=C + coff)
+
+
+_F32, _BF16 = torch.float32, torch.bfloat16
+# (groups, rows per group, C, affine, relu): every value of groups 1 / 3 / 8, rows 515 / 4096, C 72 / 256, InstanceNorm's
+# gamma = 1, beta = 0 (cyclegan._inorm) and a general gamma / beta, ReLU on and off
+_BN2_CASES = [(1, 515, 72, 'unit', True), (3, 4096, 72, 'general', False), (8, 515, 256, 'general', True),
+              (3, 515, 256, 'unit', False), (8, 4096, 256, 'unit', True), (1, 4096, 72, 'general', True)]
+
+
+@pytest.mark.parametrize('G,M,C,affine,relu', _BN2_CASES)
+@pytest.mark.parametrize('use_y2', [False, True], ids=['noy2', 'y2'])
+@pytest.mark.parametrize('use_res', [False, True], ids=['nores', 'res32'])
+@pytest.mark.parametrize('ydt', [_F32, _BF16], ids=['y32', 'y16'])
+@pytest.mark.parametrize('xdt', [_F32, _BF16], ids=['x32', 'x16'])
+def test_bn_train_fwd2(tgt, xdt, ydt, use_res, use_y2, G, M, C, affine, relu):
+    """cmda_bn_train_fwd2 (the generator's InstanceNorm: one group per sample) against float64: x and y of independent storage types,
+    the fp32 residual added AFTER the ReLU, the bf16 copy y2 with pitch C whatever ldy is, y a column slice (ldy > C, coff > 0)"""
+    ld, coff = C + 24, 16
+    x, g, b, gen = _bn_inputs(M, C, G, xdt, G * M + C)
+    if affine == 'unit':
+        g, b = torch.ones(C), torch.zeros(C)
+    res = torch.randn(G * M, C, generator=gen) * 2 if use_res else None
+    mean, var, rstd, xhat, pre = _bn_ref64(x, g, b, 1e-5)
+    ref = (pre.clamp_(min=0) if relu else pre).view(G * M, C)
+    if use_res:
+        ref = ref + res.double()
+    y = torch.zeros(G * M, ld, dtype=ydt, device=tgt.device)
+    # y2 is allocated with y's pitch and NaN-filled: the copy must land in the first G*M*C elements, at pitch C
+    y2 = torch.full((G * M * ld,), float('nan'), dtype=_BF16, device=tgt.device) if use_y2 else None
+    mean_k, rstd_k = ops.bn_train_fwd2(tgt.to(x.view(G * M, C)), tgt.to(g), tgt.to(b), y, M, C, 1e-5, relu, groups=G, res32=tgt.to(res),
+                                       y2=y2, ldy=ld, coff=coff)
+    # y: the fp32 result (3e-5, DT) or ONE bf16 rounding of it (4e-3: at most 2^-8 of the largest element)
+    assert_close(y[:, coff:coff + C], ref, 3e-5 if ydt == _F32 else 4e-3, name='bn fwd2 y')
+    assert not y[:, :coff].any().item() and not y[:, coff + C:].any().item(), 'columns outside the slice were written'
+    assert_close(mean_k, mean, 1e-5, name='bn fwd2 mean')
+    assert_close(rstd_k, rstd, 1e-5, name='bn fwd2 rstd')
+    if use_y2:
+        assert_close(y2[:G * M * C].view(G * M, C), ref, 4e-3, name='bn fwd2 y2')
+        assert bool(y2[G * M * C:].isnan().all()), 'y2 written past its [rows, C] extent'
+
+
+@pytest.mark.parametrize('ydt', [_F32, _BF16], ids=['y32', 'y16'])
+def test_bn_train_fwd2_epilogue_statistics(tgt, ydt):
+    """the stats_ws form: the statistics come from the producing GEMM's epilogue (ops.gemm(colstats=...)), no pass over x; checked
+    against float64 statistics of the stored GEMM output, and the workspace comes back zeroed"""
+    from cmda_amd import _lib as L
+    torch.manual_seed(11)
+    G, M, C, K, ld, coff = 3, 512, 72, 96, 96, 16
+    a, w, bias = torch.randn(G * M, K), torch.randn(C, K), torch.randn(C) * 2 + 0.5
+    ad, wd = tgt.to(a), tgt.to(w)
+    ws = torch.zeros(G * int(L.lib().cmda_bn_ws_floats(C)), device=tgt.device)
+    x = torch.empty(G * M, C, device=tgt.device)
+    assert ops.colstats_ok(M, C)
+    ops.gemm(ops.plain_view(ad, G * M, K), ops.plain_view(wd, C, K), x, G * M, C, K, dtype=0, bias=tgt.to(bias), colstats=(ws, M))
+    assert ws.abs().max().item() > 0
+    g, b = torch.rand(C) + 0.5, torch.randn(C)
+    res = torch.randn(G * M, C)
+    mean, var, rstd, xhat, pre = _bn_ref64(x.cpu().view(G, M, C), g, b, 1e-5)
+    ref = pre.clamp_(min=0).view(G * M, C) + res.double()
+    y = torch.zeros(G * M, ld, dtype=ydt, device=tgt.device)
+    mean_k, rstd_k = ops.bn_train_fwd2(x, tgt.to(g), tgt.to(b), y, M, C, 1e-5, True, groups=G, res32=tgt.to(res), ldy=ld, coff=coff,
+                                       stats_ws=ws)
+    assert_close(y[:, coff:coff + C], ref, 3e-5 if ydt == _F32 else 4e-3, name='bn fwd2 (epilogue statistics) y')
+    assert not y[:, :coff].any().item() and not y[:, coff + C:].any().item()
+    assert_close(mean_k, mean, 1e-5, name='bn fwd2 (epilogue statistics) mean')
+    assert_close(rstd_k, rstd, 1e-5, name='bn fwd2 (epilogue statistics) rstd')
+    assert ws.abs().max().item() == 0.0, 'the workspace comes back zeroed'
+
+
+@pytest.mark.parametrize('dt,tol', DT)
+@pytest.mark.parametrize('relu', [True, False])
+@pytest.mark.parametrize('C', [40, 516])
+@pytest.mark.parametrize('M', [1, 777, 40000])
+def test_bn_apply(tgt, dt, tol, relu, M, C):
+    """cmda_bn_apply (every eval-mode BatchNorm): y = relu?((x - mean) rstd gamma + beta) with given statistics, stored into a
+    column slice, against float64"""
+    gen = torch.Generator().manual_seed(M + C)
+    ld, coff = C + 12, 8
+    x = (torch.randn(M, C, generator=gen) * 2 + 3).to(dt)
+    mean, rstd = torch.randn(C, generator=gen) + 3, torch.rand(C, generator=gen) + 0.3
+    g, b = torch.rand(C, generator=gen) + 0.5, torch.randn(C, generator=gen) * 0.2
+    ref = (x.double() - mean.double()) * rstd.double() * g.double() + b.double()
+    ref = ref.clamp_(min=0) if relu else ref
+    y = torch.zeros(M, ld, dtype=dt, device=tgt.device)
+    ops.bn_apply(tgt.to(x), tgt.to(mean), tgt.to(rstd), tgt.to(g), tgt.to(b), y, M, C, relu, ld, coff)
+    assert_close(y[:, coff:coff + C], ref, tol, name='bn apply')
+    assert not y[:, :coff].any().item() and not y[:, coff + C:].any().item(), 'columns outside the slice were written'
+
+
+# Conditioning of the one-pass variance.  The statistics pass accumulates sum d and sum d^2 of d = x - s around the shift s = row 0
+# of the group (the contract in the header of batchnorm.hip) and forms var = E[d^2] - E[d]^2; the fused path (sums from a GEMM
+# epilogue) has s = 0.  The cancellation loses a factor kappa = 1 + (mu - s)^2 / sigma^2, so the relative error of the variance is
+# bounded by K * 2^-24 * kappa with kappa computed per channel from the float64 reference.  Dropping or breaking the shift fails the
+# mu / sigma = 1000 case by six orders of magnitude.
+# K: the worst err / (2^-24 kappa) over the sweep below against float64 was 5.121 on the emulator (ratio10_row0zero, sums) and 4.548 on
+# an MI355X (the same case, two runs; fp32 atomics reorder the GPU's sums from run to run); K = 4 x the larger.  The two agree within 15 %:
+# the constant is the rounding of sum d^2 and of E[d]^2, not of the summation order.  With row 0 an outlier (x ~ N(1000, 1) and row
+# 0 = 0, or N(0, 1) and row 0 = 1000) the shift protects nothing: kappa = 4.1e3, the variance is 6.5e-4 off (rstd 3e-4) where torch's
+# two-pass fp32 BatchNorm is at 1e-6 -- inside this bound, and stated here so that a rewrite changes it knowingly.
+_BN_COND_K = 20.5
+_BN_COND = {'ratio0': (0.0, None), 'ratio10': (10.0, None), 'ratio1000': (1000.0, None),
+            'ratio0_row0zero': (0.0, 0.0), 'ratio10_row0zero': (10.0, 0.0), 'ratio1000_row0zero': (1000.0, 0.0),
+            'ratio0_row0at1000': (0.0, 1000.0)}
+
+
+@pytest.mark.parametrize('path', ['statistics_pass', 'epilogue_sums'])
+@pytest.mark.parametrize('case', list(_BN_COND))
+def test_batchnorm_conditioning(tgt, case, path):
+    """fp32, no ReLU, 4096 x 64 against float64: x ~ N(mu, 1) with mu / sigma in {0, 10, 1000}, the same with row 0 replaced by 0, and
+    N(0, 1) with row 0 = 1000; through the statistics pass (shift = row 0) and from epilogue sums (no shift).  The variance is read
+    back from the saved rstd."""
+    from cmda_amd import _lib as L
+    M, C, eps = 4096, 64, 1e-5
+    ratio, row0 = _BN_COND[case]
+    gen = torch.Generator().manual_seed(int(ratio) + 1)
+    x = torch.randn(M, C, generator=gen) + ratio      # N(mu, 1), mu / sigma = ratio
+    if row0 is not None:
+        x[0] = row0
+    x64 = x.double()
+    mu = x64.mean(0)
+    var = ((x64 - mu) ** 2).mean(0)
+    s = x64[0] if path == 'statistics_pass' else torch.zeros(C, dtype=torch.float64)
+    kappa = 1 + (mu - s) ** 2 / var
+    xd = tgt.to(x)
+    y = torch.empty(M, C, device=tgt.device)
+    ws = None
+    if path == 'epilogue_sums':   # the workspace as a GEMM epilogue leaves it: [slot][sum | sum of squares][C], float64 sums rounded once
+        ws = torch.zeros(int(L.lib().cmda_bn_ws_floats(C)))
+        wv = ws.view(33, 2, C)
+        for k, rows in enumerate(x64.chunk(32)):
+            wv[k, 0], wv[k, 1] = rows.sum(0).float(), (rows * rows).sum(0).float()
+        ws = tgt.to(ws)
+    rm, rv = torch.zeros(C, device=tgt.device), torch.ones(C, device=tgt.device)
+    mean_k, rstd_k = ops.bn_train_fwd(xd, tgt.to(torch.ones(C)), tgt.to(torch.zeros(C)), y, rm, rv, M, C, eps, 0.1, False, stats_ws=ws)
+    var_k = rstd_k[0].double().cpu() ** -2 - eps
+    worst = ((var_k - var).abs() / var / (2.0 ** -24 * kappa)).max().item()
+    print(f'bn conditioning {case} {path} [{tgt.kind}]: worst var err / (2^-24 kappa) = {worst:.3f}, kappa max {kappa.max().item():.3g}, '
+          f'rel var err max {((var_k - var).abs() / var).max().item():.3g}')
+    if ws is not None:
+        assert ws.abs().max().item() == 0.0, 'the workspace comes back zeroed'
+    check_le('bn variance: relative error / (2^-24 kappa)', worst, _BN_COND_K)
+
+
+# ------------------------------------------------------------------ entry points that had no test of their own, each against torch
+@pytest.mark.parametrize('dt', [_F32, _BF16], ids=['f32', 'bf16'])
+@pytest.mark.parametrize('rows', [1, 33, 70001])
+def test_copy2d(tgt, dt, rows):
+    """cmda_copy2d: a [rows, cols] block between two row-major buffers of different pitch, both with a column offset; every element
+    outside the block keeps its value (exact: the kernel only moves values)"""
+    torch.manual_seed(rows)
+    cols, src_ld, dst_ld, src_off, dst_off = 20, 28, 36, 4, 8
+    src, dst0 = torch.randn(rows, src_ld).to(dt), torch.randn(rows, dst_ld).to(dt)
+    dst = tgt.to(dst0.clone())
+    ops.copy2d(tgt.to(src), dst, rows, cols, src_ld, dst_ld, src_off=src_off, dst_off=dst_off)
+    want = dst0.clone()
+    want[:, dst_off:dst_off + cols] = src[:, src_off:src_off + cols]
+    assert torch.equal(dst.cpu(), want)
+
+
+@pytest.mark.parametrize('dt', [_F32, _BF16], ids=['f32', 'bf16'])
+@pytest.mark.parametrize('n', [4, 1028, 4 << 20])
+def test_cast_clear(tgt, dt, n):
+    """cmda_cast_clear: the result is the cast of the fp32 source (one rounding for bf16: exact against torch's), the source is all
+    zero afterwards"""
+    torch.manual_seed(n)
+    src = torch.randn(n)
+    sd = tgt.to(src.clone())
+    out = ops.cast_clear(sd, dt)
+    assert out.dtype == dt and torch.equal(out.cpu(), src.to(dt))
+    assert not sd.any().item(), 'the source is left zeroed'
+
+
+@pytest.mark.parametrize('dt', [_F32, _BF16], ids=['f32', 'bf16'])
+@pytest.mark.parametrize('per_channel', [False, True], ids=['per_sample', 'per_sample_channel'])
+@pytest.mark.parametrize('C', [8, 320])
+def test_sample_scale(tgt, dt, per_channel, C):
+    """cmda_sample_scale: x [B, H, W, C] times scale[b] or scale[b, c] (one fp32 product, rounded once for bf16: exact)"""
+    torch.manual_seed(C)
+    B, H, W = 3, 7, 5
+    x = torch.randn(B, H, W, C).to(dt)
+    sc = torch.rand(B, C) + 0.5 if per_channel else torch.rand(B) + 0.5
+    want = (x.float() * (sc.view(B, 1, 1, C) if per_channel else sc.view(B, 1, 1, 1))).to(dt)
+    out = ops.sample_scale(tgt.to(x), tgt.to(sc), B, C, per_channel=per_channel)
+    assert torch.equal(out.cpu(), want)
+
+
+@pytest.mark.parametrize('nc', [19, 7])
+@pytest.mark.parametrize('h,w,H,W', [(8, 8, 32, 32), (6, 10, 24, 40), (7, 5, 28, 20), (8, 8, 8, 8), (5, 7, 13, 18), (2, 3, 32, 48), (9, 17, 36, 68),
+                                     (12, 20, 24, 40), (10, 9, 30, 27), (32, 40, 128, 160), (11, 13, 66, 65)])
+def test_upsample_logits_nchw(tgt, h, w, H, W, nc):
+    """cmda_upsample_logits_nchw (the checker of test_dacs.py / test_image_uda.py, checked itself here) against F.interpolate at the
+    size pairs of test_ce_upsample: integer and non-integer ratios, identity"""
+    torch.manual_seed(h * 3 + w + nc)
+    logits = torch.randn(2, h, w, nc) * 2
+    ref = F.interpolate(logits.double().permute(0, 3, 1, 2), size=(H, W), mode='bilinear', align_corners=False)
+    out = ops.upsample_logits_nchw(tgt.to(logits), H, W)
+    assert out.shape == (2, nc, H, W)
+    # torch's own fp32 F.interpolate is up to 1.04e-6 of the largest element off the float64 reference at these sizes (the non-integer
+    # ratios: the fp32 source coordinate), the kernel 1.06e-6 on an MI355X; the bound is 4 x torch's
+    assert_close(out, ref, 4e-6, name='upsample logits nchw')
+
+
+def _permute_desc(n):
+    import numpy as np
+    return np.zeros(n, dtype=[('src', '<u8'), ('dst', '<u8'), ('d', '<i4', 4), ('p', '<i4', 4), ('flip', '<i4'), ('mode', '<i4'),
+                              ('total', '<i8')])
+
+
+def test_permute4_batch(tgt):
+    """cmda_permute4_batch, all three code paths in ONE launch over tensors of different shapes.  General path: axis flips; channel
+    padding (Ci = 3 -> 8, bf16 and fp32 destination, padded entries zero); a (0, 2, 3, 1) permutation whose total is not a multiple
+    of 4.  Fast path: (0, 2, 3, 1) with an aligned source and a total that is.  Drain mode (records built by ops._conv_drain_plan):
+    gradient += shadow in [Co, Ci, KH, KW] order, shadow cleared; with and without channel-padded shadows, totals that are not
+    multiples of 4 or of the 1024-element chunk, and an all-zero shadow that leaves its gradient bit-identical."""
+    import numpy as np
+    torch.manual_seed(12)
+    dev = tgt.device
+    keep, recs, checks = [], [], []
+
+    def plain(src, dims, perm, flip, dst_dt, want):
+        """one non-drain record; dims = the (padded) dims the destination is laid out with"""
+        s = tgt.to(src.contiguous())
+        dst = torch.full(want.shape, float('nan'), dtype=dst_dt, device=dev)
+        keep.extend([s, dst])
+        recs.append((s.data_ptr(), dst.data_ptr(), tuple(dims), tuple(perm), flip, int(dst_dt == _BF16), want.numel()))
+        checks.append((dst, want.to(dst_dt)))
+
+    w = torch.randn(6, 5, 3, 3)
+    plain(w, (6, 5, 3, 3), (1, 2, 3, 0), 0b1100, _F32, w.flip(2, 3).permute(1, 2, 3, 0).contiguous())     # general, flips
+    plain(w, (6, 5, 3, 3), (1, 2, 3, 0), 0b1100, _BF16, w.flip(2, 3).permute(1, 2, 3, 0).contiguous())
+    w3 = torch.randn(16, 3, 7, 7)                                                                           # general, Ci 3 -> 8
+    padded = torch.zeros(16, 7, 7, 8)
+    padded[..., :3] = w3.permute(0, 2, 3, 1)
+    plain(w3, (16, 8, 7, 7), (0, 2, 3, 1), (2 << 8) | (3 << 16), _BF16, padded)
+    plain(w3, (16, 8, 7, 7), (0, 2, 3, 1), (2 << 8) | (3 << 16), _F32, padded)
+    wf = torch.randn(8, 33, 3, 3)                                                                           # fast path: 2376 = 4 * 594
+    assert wf.numel() % 4 == 0 and wf.numel() % 1024
+    plain(wf, (8, 33, 3, 3), (0, 2, 3, 1), 0, _F32, wf.permute(0, 2, 3, 1).contiguous())
+    plain(wf, (8, 33, 3, 3), (0, 2, 3, 1), 0, _BF16, wf.permute(0, 2, 3, 1).contiguous())
+    wg = torch.randn(7, 5, 3, 3)                                                                            # same permutation, total 315: general
+    assert wg.numel() % 4
+    plain(wg, (7, 5, 3, 3), (0, 2, 3, 1), 0, _F32, wg.permute(0, 2, 3, 1).contiguous())
+    assert all(k.data_ptr() % 16 == 0 for k in keep)
+    # drain records: (gradient shape, padded channel count of the shadow or 0, all-zero shadow)
+    drains = []
+    for (Co, Ci, KH, KW), cs, zero in [((16, 3, 7, 7), 8, False), ((5, 7, 3, 3), 0, False), ((64, 40, 3, 3), 0, False),
+                                       ((9, 3, 3, 3), 4, False), ((6, 5, 3, 3), 0, True)]:
+        cs = cs or Ci
+        sh = torch.zeros(Co, KH, KW, cs) if zero else torch.randn(Co, KH, KW, cs)   # (the padded channels carry GEMM sums too)
+        g0 = torch.randn(Co, Ci, KH, KW)
+        if zero:
+            g0[0, 0, 0, 0] = -0.0   # (a stored sum would turn it into +0)
+        shd, gd = tgt.to(sh.view(Co, KH * KW * cs).clone()), tgt.to(g0.clone())
+        drains.append((sh, g0, shd, gd, Ci, cs, zero))
+    assert [d[1].numel() % 4 != 0 for d in drains].count(True) >= 2 and all(d[1].numel() % 1024 for d in drains)
+    dtab, dblk, dn = ops._conv_drain_plan(dev, [(d[2], d[3]) for d in drains])
+    drec = dtab.cpu().numpy().view(_permute_desc(1).dtype)
+    desc = _permute_desc(len(recs) + len(drec))
+    for i, r in enumerate(recs):
+        desc[i] = r
+    desc[len(recs):] = drec
+    blocks = [(i, c) for i, r in enumerate(recs) for c in range((r[6] + 1023) // 1024)]
+    dblocks = dblk.cpu().numpy().view(np.int32).reshape(-1, 2).copy()
+    assert len(dblocks) == dn
+    dblocks[:, 0] += len(recs)
+    blocks = np.concatenate([np.asarray(blocks, dtype=np.int32), dblocks])
+    tab = tgt.to(torch.from_numpy(desc.view(np.uint8).reshape(-1).copy()))
+    blk = tgt.to(torch.from_numpy(blocks.copy()))
+    ops.permute4_batch(tab, blk, len(blocks))
+    for dst, want in checks:
+        assert torch.equal(dst.cpu(), want)          # moves (and rounds once for bf16): exact
+    for sh, g0, shd, gd, Ci, cs, zero in drains:
+        Co, _, KH, KW = g0.shape
+        want = g0 + sh[..., :Ci].permute(0, 3, 1, 2)  # one fp32 addition per element: exact
+        if zero:
+            assert torch.equal(gd.cpu().view(torch.int32), g0.view(torch.int32)), 'an all-zero shadow must leave the gradient bit-identical'
+        else:
+            assert torch.equal(gd.cpu(), want)
+        assert not shd.view(Co, KH, KW, cs)[..., :Ci].any().item(), 'the shadow is left zeroed in its real channels'
+
+
+def test_layernorm_deferred_parameter_gradients(tgt):
+    """the deferred form of cmda_layernorm_bwd2 (dgamma == NULL: the partial sums stay in the layer's workspace) and
+    cmda_layernorm_fold_batch: inside ops.backward_scope several layers of different width (C = 1024 needs four 256-channel
+    chunks, whose blocks return early for the narrow layers), one of them with two backward calls before the fold, dgamma / dbeta
+    pre-filled; after the scope they hold the float64 sums and every layer's workspace is zero.  The immediate form gives the same."""
+    from cmda_amd import deferred as D
+    torch.manual_seed(21)
+    layers = []
+    for C, rows, calls in [(32, 37, 1), (320, 9001, 2), (1024, 37, 1), (32, 9001, 1), (1024, 9001, 1)]:
+        g = torch.randn(C)
+        xs = [torch.randn(rows, C) * 2 + 1 for _ in range(calls)]
+        dys = [torch.randn(rows, C) for _ in range(calls)]
+        dg0, db0 = torch.randn(C), torch.randn(C)
+        dgr, dbr = dg0.double(), db0.double()
+        for x, dy in zip(xs, dys):
+            x64 = x.double()
+            mu = x64.mean(1, keepdim=True)
+            xhat = (x64 - mu) * (((x64 - mu) ** 2).mean(1, keepdim=True) + 1e-6).rsqrt()
+            dgr, dbr = dgr + (dy.double() * xhat).sum(0), dbr + dy.double().sum(0)
+        layers.append(dict(C=C, g=tgt.to(g), xs=[tgt.to(x) for x in xs], dys=[tgt.to(d) for d in dys], dg0=dg0, db0=db0, dgr=dgr, dbr=dbr))
+
+    def run(deferred):
+        out = []
+        for l in layers:
+            l['dg'], l['db'] = tgt.to(l['dg0'].clone()), tgt.to(l['db0'].clone())
+            out.append((l['dg'], l['db']))
+        for l in layers:
+            for x, dy in zip(l['xs'], l['dys']):
+                _, mean, rstd = ops.layernorm_fwd(x, l['g'], torch.zeros_like(l['g']), 1e-6)
+                ops.layernorm_bwd(dy, x, l['g'], mean, rstd, l['dg'], l['db'])
+                if deferred:
+                    assert torch.equal(l['dg'].cpu(), l['dg0']), 'deferred: nothing reaches dgamma before the fold'
+        return out
+
+    D.reset()
+    with ops.backward_scope():
+        got = run(True)
+        regions = [D.LN.regions[dg.data_ptr()] for dg, _ in got]
+        assert all(r[0].abs().max().item() > 0 for r in regions)
+    for l, (dg, db), r in zip(layers, got, regions):
+        assert_close(dg, l['dgr'], 2e-5, name=f'deferred ln dgamma C={l["C"]}')    # (the bounds of test_layernorm)
+        assert_close(db, l['dbr'], 2e-5, name=f'deferred ln dbeta C={l["C"]}')
+        assert r[0].abs().max().item() == 0.0, 'the fold leaves every region zeroed'
+    deferred = [(dg.cpu(), db.cpu()) for dg, db in got]
+    for l, (dg, db), (dg_d, db_d) in zip(layers, run(False), deferred):
+        assert_close(dg, l['dgr'], 2e-5, name=f'immediate ln dgamma C={l["C"]}')
+        assert_close(dg, dg_d, 2e-5, name=f'ln dgamma: immediate against deferred C={l["C"]}')
+        assert_close(db, db_d, 2e-5, name=f'ln dbeta: immediate against deferred C={l["C"]}')
+
+
+@pytest.mark.parametrize('dt,tol', DT)
+def test_layernorm_single_dtype_entry_points(tgt, dt, tol):
+    """cmda_layernorm_fwd / cmda_layernorm_bwd: the one-dtype forms of the ABI (no Python wrapper calls them) against float64, and
+    the queries the backward's workspace is sized with: cmda_layernorm_slots x 2 x C = cmda_layernorm_bwd_ws_floats"""
+    from cmda_amd import _lib as L
+    torch.manual_seed(8)
+    rows, C = 301, 160
+    x, dy = (torch.randn(rows, C) * 2 + 1).to(dt), torch.randn(rows, C).to(dt)
+    g, b = torch.randn(C), torch.randn(C)
+    x64 = x.double()
+    mu = x64.mean(1, keepdim=True)
+    rs = (((x64 - mu) ** 2).mean(1, keepdim=True) + 1e-6).rsqrt()
+    xhat = (x64 - mu) * rs
+    gy = dy.double() * g.double()
+    dxref = rs * (gy - gy.mean(1, keepdim=True) - xhat * (gy * xhat).mean(1, keepdim=True))
+    xd, dyd, gd, bd = map(tgt.to, (x, dy, g, b))
+    y = torch.empty_like(xd)
+    mean, rstd = torch.empty(rows, device=tgt.device), torch.empty(rows, device=tgt.device)
+    st = L.stream_of(xd)
+    L.call('cmda_layernorm_fwd', L.ptr(xd), L.ptr(gd), L.ptr(bd), L.ptr(y), L.ptr(mean), L.ptr(rstd), L.c_i64(rows), L.c_i32(C),
+           L.c_f32(1e-6), L.dtype_tag(xd), st)
+    assert_close(y, xhat * g.double() + b.double(), tol, name='ln fwd (one-dtype entry point)')
+    assert_close(mean, mu[:, 0], 1e-5, name='ln mean (one-dtype entry point)')
+    slots = int(L.lib().cmda_layernorm_slots())
+    assert slots > 0 and slots * 2 * C == int(L.lib().cmda_layernorm_bwd_ws_floats(rows, C))
+    ws = torch.zeros(slots * 2 * C, device=tgt.device)
+    dx = torch.empty_like(dyd)
+    dg, db = torch.zeros(C, device=tgt.device), torch.zeros(C, device=tgt.device)
+    L.call('cmda_layernorm_bwd', L.ptr(dyd), L.ptr(xd), L.ptr(gd), L.ptr(mean), L.ptr(rstd), None, L.ptr(dx), L.ptr(dg), L.ptr(db),
+           L.ptr(ws), L.c_i64(rows), L.c_i32(C), None, L.c_i64(0), None, L.dtype_tag(xd), st)
+    assert_close(dx, dxref, tol, name='ln dx (one-dtype entry point)')
+    assert_close(dg, (dy.double() * xhat).sum(0), 2e-5, name='ln dgamma (one-dtype entry point)')
+    assert_close(db, dy.double().sum(0), 2e-5, name='ln dbeta (one-dtype entry point)')
+    assert ws.abs().max().item() == 0.0, 'the workspace is zero again when the call completes'
