@@ -17,14 +17,9 @@
 //
 // MFMA-bound per block but small: per 16 queries 32 + 32 v_mfma_f32_16x16x32_bf16.  HBM traffic per (batch, head):
 // Q, O once, K, V once per 128-query block (L2 hits).  Algorithmic bytes per query: 2 * 64 * 2 (q, o) + the K/V share.
-#include "common.h"
+#include "attention_common.h"
 
 namespace {
-
-constexpr int kHD = 64;     // head dim
-constexpr int kMaxK = 256;  // keys kept in LDS (forward and backward)
-constexpr int kMaxKFwd = 320;  // ... by the forward-only instance
-constexpr int kNT = kMaxK / 16;
 
 struct AttnParams {
   const bf16_t* q;   // [B*N, C]
@@ -34,110 +29,6 @@ struct AttnParams {
   float scale;
   int q_per_block;
 };
-
-// XCD-aware block order: workgroups are dealt round-robin to the 8 XCDs (one L2 each).  All query blocks of one
-// (batch, head) read the same K / V, so the 1-D grid is remapped to give each XCD a contiguous band of logical blocks
-// (query block fastest): a (batch, head)'s K / V then comes through ONE L2 instead of eight (PMC: 67 MB fetched per
-// launch against 17 MB written before this).
-static __device__ __forceinline__ unsigned xcd_logical_block() {
-  const unsigned nb = gridDim.x, lin = blockIdx.x;
-  const unsigned q = nb / 8, r = nb % 8, xcd = lin % 8, loc = lin / 8;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-}
-
-// K or V of one (batch, head) -> LDS [kMaxK][64] bf16, 128-byte lines, 16-byte chunk c of line r stored at slot c ^ (r & 7);
-// rows >= Nk come from the zero block.  One DMA instruction moves 8 lines (1 KiB); the 4 waves take 8 instructions each.
-extern __device__ __attribute__((aligned(16))) unsigned g_attn_zero16[4];
-__device__ __attribute__((aligned(16))) unsigned g_attn_zero16[4] = {0u, 0u, 0u, 0u};
-
-template <int MAXK = kMaxK>
-static __device__ __forceinline__ void load_kv_tile(const bf16_t* __restrict__ src, int ld, int Nk, bf16_t* lds, int wid,
-                                                    int lane, int nwaves) {
-  for (int i = wid; i < MAXK / 8; i += nwaves) {
-    const int row = 8 * i + (lane >> 3);
-    const int chunk = (lane & 7) ^ (row & 7);
-    const void* s = row < Nk ? static_cast<const void*>(src + (long)row * ld + chunk * 8)
-                             : static_cast<const void*>(g_attn_zero16);
-    glds16(s, reinterpret_cast<char*>(lds) + i * 1024);
-  }
-}
-
-// A operand (rows = 16 consecutive tile rows, k = 32 consecutive d) of a row-major swizzled [rows][64] tile
-static __device__ __forceinline__ u16x8 frag_rows(const bf16_t* tile, int row0, int kk, int g, int l15) {
-  const int row = row0 + l15;
-  return *reinterpret_cast<const u16x8*>(&tile[row * kHD + (((kk * 4 + g) ^ (row & 7)) << 3)]);
-}
-
-// A operand of the transposed tile: rows = d (16dt + l15), k slot (g, j) = tile row R0 + j (j < 4) / R1 + (j - 4)
-static __device__ __forceinline__ u16x8 frag_cols(const bf16_t* tile, int R0, int R1, int dt, int l15) {
-  const int q = l15 >> 2, pp = l15 & 3;
-  const int r0 = R0 + q, r1 = R1 + q;
-  const int cidx = 2 * dt + (pp >> 1), half = (pp & 1) << 2;
-  const u16x4 lo = lds_read_tr16(&tile[r0 * kHD + ((cidx ^ (r0 & 7)) << 3) + half]);
-  const u16x4 hi = lds_read_tr16(&tile[r1 * kHD + ((cidx ^ (r1 & 7)) << 3) + half]);
-  return u16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-
-static __device__ __forceinline__ float col_max(float v) {  // over the 4 lane groups holding one query column
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-static __device__ __forceinline__ float col_sum(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
-
-// scores^T of 16 queries against all key tiles, then the softmax over keys: p[t][r] = P^T[key 16t + 4g + r][query l15]
-template <int NT = kNT>
-static __device__ __forceinline__ void scores_softmax(const bf16_t* sK, const u16x8 (&qf)[2], int nt, int Nk, float scale,
-                                                      int g, int l15, f32x4 (&p)[NT], float* lse_out = nullptr) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    p[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (t < nt) {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) p[t] = mfma_bf16_16x16x32(frag_rows(sK, 16 * t, kk, g, l15), qf[kk], p[t]);
-    }
-  }
-  float m = -INFINITY;
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const bool live = 16 * t + 4 * g + r < Nk;
-      p[t][r] = live ? p[t][r] * scale : -INFINITY;
-      m = fmaxf(m, p[t][r]);
-    }
-  m = col_max(m);
-  float l = 0.f;
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      p[t][r] = __expf(p[t][r] - m);  // exp(-inf) = 0 for the masked keys
-      l += p[t][r];
-    }
-  l = col_sum(l);
-  if (lse_out) *lse_out = m + __logf(l);
-  const float inv = 1.f / l;
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) p[t][r] *= inv;
-}
-
-static __device__ __forceinline__ u16x8 pack_pair(const f32x4& a, const f32x4& b) {
-  return u16x8{f2bf(a[0]), f2bf(a[1]), f2bf(a[2]), f2bf(a[3]), f2bf(b[0]), f2bf(b[1]), f2bf(b[2]), f2bf(b[3])};
-}
-
-// B operand b[k = d][col = query]: 16 bytes of row (row0 + l15) of a [rows, ld] global matrix; rows past `nrows` repeat the last
-static __device__ __forceinline__ void load_qfrag(const bf16_t* __restrict__ base, long row0, long nrows, int ld, int g,
-                                                  int l15, u16x8 (&f)[2]) {
-  long row = row0 + l15;
-  if (row >= nrows) row = nrows - 1;
-#pragma unroll
-  for (int kk = 0; kk < 2; ++kk) f[kk] = *reinterpret_cast<const u16x8*>(base + row * ld + 32 * kk + 8 * g);
-}
 
 // queries per block of the forward-shaped kernels: 64 (one pass of 4 waves x 16) or 128 (two passes, K/V loaded once for
 // both) -- the launcher takes 64 while that still leaves the grid under ~4 blocks per CU (stage 3: 27.4 -> 22.9 us)
@@ -288,7 +179,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
   }
 }
 
-constexpr int kKS = 64;        // keys per dK/dV block
 constexpr int kRedPitch = 68;  // floats per key row of the cross-wave reduction buffer
 
 // NW waves per block: 4 (two blocks per CU when the queries are split into spans) or 8 (direct mode: one block per key slice walks
@@ -849,13 +739,20 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_x3_kernel(AttnBwdX3Params
 
 }  // namespace
 
-// q [B*N, C] bf16, kv [B*Nk, 2C] bf16 -> o [B*N, C] bf16; head_dim = C / heads must be 64, Nk <= 320 (the backward: 256), C % 8 == 0.
+// head dim C / heads: 64 (the kernels above) or a larger multiple of 64 up to 1024 (attention_wide.hip)
+static inline bool head_dim_ok(int heads, int C) {
+  const int hd = C / heads;
+  return C == heads * hd && hd % kHD == 0 && hd >= kHD && hd <= 1024;
+}
+
+// q [B*N, C] bf16, kv [B*Nk, 2C] bf16 -> o [B*N, C] bf16; head_dim = C / heads in {64, 128, ..., 1024}, Nk <= 320 (the backward: 256).
 extern "C" int cmda_attention_fwd(const void* q, const void* kv, void* o, int B, int N, int Nk, int heads, int C,
                                   float scale, int dtype, void* stream) {
   if (B <= 0 || N <= 0) return CMDA_OK;
   if (dtype != CMDA_BF16) return CMDA_ERR_DTYPE;
-  if (heads <= 0 || C != heads * kHD || Nk <= 0 || Nk > kMaxKFwd) return CMDA_ERR_UNSUPPORTED;
+  if (heads <= 0 || Nk <= 0 || Nk > kMaxKFwd || !head_dim_ok(heads, C)) return CMDA_ERR_UNSUPPORTED;
   if (heads > 65535 || B > 65535) return CMDA_ERR_SHAPE;
+  if (C != heads * kHD) return attn_wide_fwd(q, kv, o, B, N, Nk, heads, C, scale, stream);
   const int qpb = fwd_queries_per_block(B, N, heads);
   AttnParams p{(const bf16_t*)q, (const bf16_t*)kv, (bf16_t*)o, B, N, Nk, heads, C, scale, qpb};
   const long nblk = (long)((N + qpb - 1) / qpb) * heads * B;
@@ -866,7 +763,7 @@ extern "C" int cmda_attention_fwd(const void* q, const void* kv, void* o, int B,
   CMDA_CHECK_LAUNCH();
 }
 
-// d_o [B*N, C] bf16 -> dq [B*N, C] bf16 (written), dkv32 [B*Nk, 2C] fp32 (accumulated: dK | dV).
+// d_o [B*N, C] bf16 -> dq [B*N, C] bf16 (written), dkv32 [B*Nk, 2C] fp32 (accumulated: dK | dV; required when head_dim > 64).
 // stats: scratch of cmda_attention_bwd_ws_floats(B, N, heads) floats.
 extern "C" int64_t cmda_attention_bwd_ws_floats(int B, int N, int heads) { return (int64_t)B * N * heads * 2; }
 
@@ -882,8 +779,12 @@ extern "C" int cmda_attention_bwd(const void* q, const void* kv, const void* d_o
                                   float* stats, int B, int N, int Nk, int heads, int C, float scale, int dtype, void* stream) {
   if (B <= 0 || N <= 0) return CMDA_OK;
   if (dtype != CMDA_BF16) return CMDA_ERR_DTYPE;
-  if (heads <= 0 || C != heads * kHD || Nk <= 0 || Nk > kMaxK) return CMDA_ERR_UNSUPPORTED;
+  if (heads <= 0 || Nk <= 0 || Nk > kMaxK || !head_dim_ok(heads, C)) return CMDA_ERR_UNSUPPORTED;
   if (heads * 4 > 65535 || B > 65535) return CMDA_ERR_SHAPE;
+  if (C != heads * kHD) {  // wide heads: accumulating form only (cmda_attention_bwd_direct knows no head dim)
+    if (dkv32 == nullptr) return CMDA_ERR_SHAPE;
+    return attn_wide_bwd(q, kv, d_o, dq, dkv32, stats, B, N, Nk, heads, C, scale, stream);
+  }
   const bool direct = cmda_attention_bwd_direct(B, N, Nk, heads) != 0 && dkv16 != nullptr;
   if (!direct && dkv32 == nullptr) return CMDA_ERR_SHAPE;
   const int fqpb = fwd_queries_per_block(B, N, heads);

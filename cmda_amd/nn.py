@@ -121,7 +121,8 @@ def _conv_bwd(dy, x, weight, bias, B, H, W, stride, pad, dil=1, *, need_dx=True,
 # ------------------------------------------------------------------ attention (scores materialised; v0 path)
 def attention_fwd(q, kv, B, N, Nk, heads, C, scale, need_grad=True):
     """q [B*N,C], kv [B*Nk,2C] -> o [B*N,C]; returns (o, P): P [B,heads,N,Nk] saved for the backward, or None when the fused
-    kernel ran (bf16 -- or fp32 storage in the split-bf16 mode --, head_dim 64, Nk <= 256: the backward recomputes the probabilities in LDS)."""
+    kernel ran (bf16, head_dim 64 ... 1024 -- or fp32 storage in the split-bf16 mode, head_dim 64 --, Nk <= 256: the backward recomputes
+    the probabilities in LDS)."""
     if ops.attention_fused_ok(q, Nk, heads, C, need_grad, x3=rt.gemm_x3()) and not os.environ.get('CMDA_NO_FUSED_ATTENTION'):
         return ops.attention_fused_fwd(q, kv, B, N, Nk, heads, C, scale), None
     hd = C // heads
@@ -145,13 +146,20 @@ def attention_bwd(do, q, kv, P, B, N, Nk, heads, C, scale):
     dev = do.device
     tag = rt.tag()
     if P is None:  # fused forward ran (bf16)
-        if ops.attention_bwd_direct(B, N, Nk, heads):   # few queries: dK | dV come out final, as bf16, from one block per key slice
+        if hd == 64 and ops.attention_bwd_direct(B, N, Nk, heads):   # few queries: dK | dV come out final, as bf16, from one block per key slice
             dkv = torch.empty(B * Nk, 2 * C, dtype=rt.compute_dtype(), device=dev)
             dq = ops.attention_fused_bwd(q, kv, do, None, B, N, Nk, heads, C, scale, dkv16=dkv)
             return dq, dkv
-        # otherwise dK | dV accumulate in the persistent zeroed workspace, drained by one cast+clear
+        # otherwise (and for every head wider than 64) dK | dV accumulate in the persistent zeroed workspace, drained by one cast+clear
         dkv32 = ops.zero_ws(dev, B * Nk * 2 * C).view(B * Nk, 2 * C)
-        dq = ops.attention_fused_bwd(q, kv, do, dkv32, B, N, Nk, heads, C, scale)
+        try:
+            dq = ops.attention_fused_bwd(q, kv, do, dkv32, B, N, Nk, heads, C, scale)
+        except Exception:
+            try:   # the workspace is zero on entry for the next user, whatever happened here; the first error is the one reported
+                ops.cast_clear(dkv32, rt.compute_dtype())
+            except Exception:
+                pass
+            raise
         return dq, ops.cast_clear(dkv32, rt.compute_dtype())
     dkv32 = torch.zeros(B * Nk, 2 * C, dtype=torch.float32, device=dev)
     Pv = dict(batch_stride=heads * N * Nk, batch2_stride=N * Nk)

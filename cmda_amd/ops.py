@@ -545,13 +545,33 @@ def softmax_bwd_(p, dp, rows, L, alpha):
     return dp
 
 
+# Wide heads (head dim > 64: the fusion modules' single-head Blocks) that take the chunked fused kernels of attention_wide.hip BY DEFAULT,
+# one entry per head dim of the two reference configs: (forward only, forward + backward).  Set from tools/attn_bench.py on the MI355X
+# (profiles/attn_wide_bench.txt): the kernels walk the head dim serially, ~2.3 us per 64-wide tile, and the fusion blocks' shapes give them
+# 8 ... 512 workgroups, so the walk wins where it is short -- fused / unfused at the configs' shapes: 128 fwd 0.32-0.51, fwd + bwd
+# 0.74-0.91; 256 fwd 0.87, fwd + bwd 1.30; 320 1.02 / 1.16; 512 1.53 / 1.63; 640 1.88 / 2.09; 1024 2.83 / 2.84.  A head dim that is slower
+# stays on the GEMM + softmax path; so does one that is not listed (not measured).
+ATTN_WIDE_TABLE = {128: (True, True), 256: (True, False), 320: (False, False), 512: (False, False), 640: (False, False),
+                   1024: (False, False)}
+
+
 def attention_fused_ok(q, Nk, heads, C, need_grad=True, x3=False):
     """the fused kernels hold every key of a (batch, head) in LDS: up to 256 with a backward pass to follow, up to 320 forward-only
     (inference on 440 x 640 frames: 260 / 280 keys, encoder_decoder.py:897-936).  x3: the split-bf16 mode (fp32 storage, runtime.gemm_x3)
-    has instances of its own -- K / V as hi + lo bf16 images in LDS, up to 256 keys"""
+    has instances of its own -- K / V as hi + lo bf16 images in LDS, up to 256 keys.  bf16 heads wider than 64 (multiples of 64 up to
+    1024) have the chunked instances; CMDA_ATTN_WIDE, read at call time (same-process A/B): unset / 1 = those ATTN_WIDE_TABLE names,
+    0 = none (GEMM + softmax), 2 = every wide head whatever the table says (kernel tests, tools/attn_bench.py)"""
     if x3 and q.dtype == torch.float32:
         return C == heads * 64 and 0 < Nk <= 256 and not ATTN_X3_OFF
-    return q.dtype == torch.bfloat16 and C == heads * 64 and 0 < Nk <= (256 if need_grad else 320)
+    if q.dtype != torch.bfloat16 or heads <= 0 or C % heads or not 0 < Nk <= (256 if need_grad else 320):
+        return False
+    hd = C // heads
+    if hd == 64:
+        return True
+    mode = os.environ.get('CMDA_ATTN_WIDE', '1')
+    if hd % 64 or not 64 < hd <= 1024 or mode == '0':
+        return False
+    return mode == '2' or ATTN_WIDE_TABLE.get(hd, (False, False))[1 if need_grad else 0]
 
 
 ATTN_X3_OFF = os.environ.get('CMDA_ATTN_X3', '1') == '0'   # split-bf16 mode on the unfused GEMM + softmax path (same-box A/B)

@@ -169,16 +169,18 @@ int cmda_layernorm_slots(void);
 int cmda_softmax_fwd(void* s, int64_t rows, int L, float alpha, int dtype, void* stream);
 int cmda_softmax_bwd(const void* p, void* dp, int64_t rows, int L, float alpha, int dtype, void* stream);
 
-/* ---- Fused attention core (bf16, head_dim 64, Nk <= 256) -- Attention.forward mix_transformer.py:86-103:
- * softmax(q k^T * scale) v per (batch, head) without materialising the [N, Nk] scores.  q [B*N, C] (head h = columns
- * 64h..), kv [B*Nk, 2C] (K at column 64h, V at C + 64h), o [B*N, C].  bwd recomputes the probabilities; dq [B*N, C] is
- * written, dkv32 [B*Nk, 2C] fp32 is ACCUMULATED into (atomics; caller zeroes).  CMDA_ERR_UNSUPPORTED outside these
- * limits (the caller then uses the GEMM + cmda_softmax path). */
+/* ---- Fused attention core (bf16, head_dim 64 ... 1024, Nk <= 256; forward-only up to 320) -- Attention.forward
+ * mix_transformer.py:86-103: softmax(q k^T * scale) v per (batch, head) without materialising the [N, Nk] scores.  hd = C / heads
+ * is 64 (the encoders) or a larger multiple of 64 up to 1024 (the fusion modules' single-head Blocks: the same product walked in
+ * 64-wide chunks).  q [B*N, C] (head h = columns hd*h..), kv [B*Nk, 2C] (K at column hd*h, V at C + hd*h), o [B*N, C].  bwd
+ * recomputes the probabilities; dq [B*N, C] is written, dkv32 [B*Nk, 2C] fp32 is ACCUMULATED into (atomics; caller zeroes).
+ * CMDA_ERR_UNSUPPORTED outside these limits (the caller then uses the GEMM + cmda_softmax path). */
 int cmda_attention_fwd(const void* q, const void* kv, void* o, int B, int N, int Nk, int heads, int C, float scale,
     int dtype, void* stream);
 int64_t cmda_attention_bwd_ws_floats(int B, int N, int heads);   /* size of `stats` (per-query log-sum-exp and D) */
 /* dK | dV: accumulated into dkv32 (fp32 [B*Nk, 2C], zero on entry) -- or, when cmda_attention_bwd_direct(...) is 1 and dkv16 is
- * given, stored as bf16 [B*Nk, 2C] into dkv16 by one block per key slice (no workspace, no atomics; dkv32 may then be NULL). */
+ * given, stored as bf16 [B*Nk, 2C] into dkv16 by one block per key slice (no workspace, no atomics; dkv32 may then be NULL).
+ * The direct mode exists for head_dim 64 only: with a wider head dkv16 is ignored and a NULL dkv32 is CMDA_ERR_SHAPE. */
 int cmda_attention_bwd_direct(int B, int N, int Nk, int heads);
 int cmda_attention_bwd(const void* q, const void* kv, const void* d_o, void* dq, float* dkv32, void* dkv16, float* stats, int B,
     int N, int Nk, int heads, int C, float scale, int dtype, void* stream);
