@@ -5,15 +5,27 @@
 //   depthwise half of DepthwiseSeparableConvModule (3x3, dilation 6/12/18, no bias) in the sep-ASPP
 //   decode_heads/sep_aspp_head.py:18-27 (mmcv DepthwiseSeparableConvModule.depthwise_conv)
 //
-// HBM-bound stencils: a thread owns 4 adjacent channels and a RUN of 8 pixels of one image row spaced `dil` apart.  It
-// first issues ALL 3 x (RUN+2) window loads (clamped addresses, zero-selected afterwards -- no branch between them, so
-// ~15 KiB per wave is in flight), then slides a 3x3 register window along the run: 3.75 coalesced 8/16-byte loads per
-// output (lanes run along C) instead of 9.  Algorithmic bytes per pixel-channel:
-// fwd 2*sizeof(T); gelu-bwd-prep 3*sizeof(T); bwd-data 2*sizeof(T); bwd-weight 2*sizeof(T).
+// HBM-bound stencils.  A thread always owns 4 adjacent channels (lanes run along C: coalesced 8/16-byte accesses); the kernels differ
+// in how it moves over the pixels:
+//  * row walk (dw_walk_kernel), bf16, dil = 1 -- the MixFFN forward + GELU, its data gradient and its fused GELU backward: 2 / 4 columns x
+//    a band of 4 ... 16 rows, walked DOWN with a ring of packed register rows; every input row is requested once per run
+//    ((WR + 2) / WR loads per output + two halo rows per band), one row ahead of the arithmetic, all loads unconditional so that the
+//    compiler counts them (s_waitcnt vmcnt(n)) instead of draining them;
+//  * sub-lattice walk (dw_dilated_kernel), dil >= 2 without activation -- the sep-ASPP branches: the same walk on each of the d x d
+//    unit-stride sub-lattices of the dilated convolution, optionally with the BatchNorm statistics of the output;
+//  * row-run stencils (dw_stencil_kernel, dw_gelu_bwd_fused_kernel, dw_bwd_weight_kernel): a RUN of 8 (fp32, fused: 4) pixels of one
+//    image row spaced `dil` apart; ALL 3 x (RUN+2) window loads are issued first (clamped addresses, zero-selected afterwards -- no
+//    branch between them, ~15 KiB per wave in flight), then a 3x3 register window slides along the run: 3.75 (4.5) loads per output
+//    and one full memory latency per run, hidden by occupancy only.  They keep what the walks do not take -- the backward prep, the
+//    weight gradient alone, fp32 (parity mode), widths that are not whole runs, dilation with an activation -- and are the row walk's bit-for-bit
+//    reference (CMDA_DW_BAND=0).
+// Algorithmic bytes per pixel-channel: fwd 2*sizeof(T); gelu-bwd-prep / fused 3*sizeof(T); bwd-data 2*sizeof(T); bwd-weight
+// 2*sizeof(T).
 // Depthwise weights/bias stay fp32.  The stencil kernels read a tap-major [9][C] copy of the reference's [C,1,3,3]
 // parameter (rt.wdw: one tiny permute per optimizer step) so that the 4 channel weights of a lane are one coalesced
-// 16-byte load per tap; the weight-gradient kernel still accumulates in the parameter's own [C,9] layout.
+// 16-byte load per tap; the weight-gradient kernels accumulate in the parameter's own [C,9] layout.
 #include "common.h"
+#include <cstdlib>
 
 namespace {
 
@@ -33,6 +45,13 @@ static inline RunGeom run_geom(int B, int H, int W, int dil, int run) {
   return g;
 }
 
+// pin(): the value stays in ITS registers as it is -- the compiler may not carry an unpacked (fp32) copy of a packed row from one row of
+// a walk to the next, which would double the window's registers
+#ifdef CMDA_EMU
+#define CMDA_DW_PIN(v) (void)(v)
+#else
+#define CMDA_DW_PIN(v) asm volatile("" : "+v"(v))
+#endif
 // raw (unconverted) 4-channel vectors: bf16 stays packed in 2 VGPRs while it waits in the prefetched window
 template <typename T> struct Raw;
 template <> struct Raw<float> {
@@ -49,10 +68,29 @@ template <> struct Raw<bf16_t> {
     v = *reinterpret_cast<const u16x4*>(p);
     if (!ok) v = (u16x4)(0);
   }
+  // (zero unless ok, by a mask and not a branch: a walk's ring rows stay where they are)
+  __device__ __forceinline__ void keep(bool ok) {
+    const unsigned long long m = ok ? ~0ull : 0ull;
+    v = __builtin_bit_cast(u16x4, __builtin_bit_cast(unsigned long long, v) & m);
+  }
+  __device__ __forceinline__ void pin() {
+    unsigned long long t = __builtin_bit_cast(unsigned long long, v);
+    CMDA_DW_PIN(t);
+    v = __builtin_bit_cast(u16x4, t);
+  }
   __device__ __forceinline__ void unpack(float (&o)[4]) const {
     o[0] = bf2f(v[0]); o[1] = bf2f(v[1]); o[2] = bf2f(v[2]); o[3] = bf2f(v[3]);
   }
 };
+// One tap of a stencil sum.  bf16: spelled fmaf -- left to the compiler's contraction, the taps on a zero-selected halo column of a
+// row-run kernel came out as multiply + add and the others fused, so the last bit of a sum depended on where its run began, and the
+// row walk, which cuts the rows elsewhere, could not reproduce it.  fp32 (parity mode) stays `c + a * b` as it always was: the walk
+// does not serve it, and the bounds of the full-model parity tests sit close to figures measured with exactly this rounding (ReLU
+// masks of the decode head flip on last bits).
+template <typename T> static __device__ __forceinline__ float tap(float a, float b, float c) {
+  if (sizeof(T) == 2) return fmaf(a, b, c);
+  return c + a * b;
+}
 template <typename T> struct RunLen { static constexpr int value = 8; };
 template <> struct RunLen<float> { static constexpr int value = 4; };  // fp32 (parity mode): half the window registers
 
@@ -155,7 +193,7 @@ __global__ __launch_bounds__(256) void dw_stencil_kernel(const T* __restrict__ x
 #pragma unroll
       for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] += win[(i + kw) % 3][kh][j] * wr[kh * 3 + kw][j];
+        for (int j = 0; j < 4; ++j) acc[j] = tap<T>(win[(i + kw) % 3][kh][j], wr[kh * 3 + kw][j], acc[j]);
     if (wx < g.W) {
       T* o = out + (r.row_base + wx) * C + c;
       if (MODE == 0) {
@@ -369,6 +407,39 @@ __global__ __launch_bounds__(256) void dw_dilated_kernel(const T* __restrict__ x
   }
 }
 
+// the 36 tap sums + 4 bias sums of a thread's channel quad: the RL run lanes of a quad meet in LDS (no LDS atomics), then ONE fp32
+// global atomic per (channel, tap) per workgroup into dw [C][9] / dbias [C]
+template <int CQ>
+static __device__ __forceinline__ void dw_fold_atomics(float (&red)[256 / CQ][CQ][41], const float (&acc)[9][4], const float (&accb)[4],
+                                                       float* __restrict__ dw, float* __restrict__ dbias, int bx, int C) {
+  constexpr int RL = 256 / CQ;
+  const int cx = threadIdx.x % CQ, py = threadIdx.x / CQ;
+  {
+    float* slot = red[py][cx];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) slot[t * 4 + j] = acc[t][j];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) slot[36 + j] = accb[j];
+  }
+  __syncthreads();
+  for (int k = threadIdx.x; k < CQ * 40; k += blockDim.x) {
+    const int gx = k / 40, v = k - gx * 40;
+    const int cc = (bx * CQ + gx) * 4;
+    if (cc >= C) continue;
+    float s = 0.f;
+#pragma unroll
+    for (int l = 0; l < RL; ++l) s += red[l][gx][v];
+    if (v < 36) {
+      const int t = v >> 2, j = v & 3;
+      atomicAdd(dw + (cc + j) * 9 + t, s);
+    } else if (dbias) {
+      atomicAdd(dbias + cc + (v - 36), s);
+    }
+  }
+}
+
 // dw[c,tap] += sum_pix dz[pix,c] * x[pix+tap,c];  dbias[c] += sum_pix dz[pix,c]
 // block = 64 channel-quads x 4 run lanes (256 threads: at ~166 VGPRs three such blocks share a CU, a 512-thread block
 // could only run alone); every thread walks runs_per_block/4 runs of its quad with the same prefetched sliding window
@@ -426,30 +497,7 @@ __global__ __launch_bounds__(256) void dw_bwd_weight_kernel(const T* __restrict_
       }
     }
   }
-  {
-    float* slot = red[py][cx];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) slot[t * 4 + j] = acc[t][j];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) slot[36 + j] = accb[j];
-  }
-  __syncthreads();
-  for (int k = threadIdx.x; k < CQ * 40; k += blockDim.x) {
-    const int gx = k / 40, v = k - gx * 40;
-    const int cc = (blk.bx * CQ + gx) * 4;
-    if (cc >= C) continue;
-    float s = 0.f;
-#pragma unroll
-    for (int l = 0; l < RL; ++l) s += red[l][gx][v];
-    if (v < 36) {
-      const int t = v >> 2, j = v & 3;
-      atomicAdd(dw + (cc + j) * 9 + t, s);
-    } else if (dbias) {
-      atomicAdd(dbias + cc + (v - 36), s);
-    }
-  }
+  dw_fold_atomics<CQ>(red, acc, accb, dw, dbias, blk.bx, C);
 }
 
 // Fused MixFFN backward step: dz = da * gelu'(conv(x) + bias)  AND  dw[c,tap] += sum dz * x[pix+tap], dbias[c] += sum dz in
@@ -513,7 +561,7 @@ __global__ __launch_bounds__(256, 2) void dw_gelu_bwd_fused_kernel(const T* __re
 #pragma unroll
           for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] += win[(i + kw) % 3][kh][j] * wr[kh * 3 + kw][j];
+            for (int j = 0; j < 4; ++j) z[j] = tap<T>(win[(i + kw) % 3][kh][j], wr[kh * 3 + kw][j], z[j]);
         float gd[4];
         rda[i].unpack(gd);  // zero beyond the row end
 #pragma unroll
@@ -530,34 +578,232 @@ __global__ __launch_bounds__(256, 2) void dw_gelu_bwd_fused_kernel(const T* __re
       }
     }
   }
-  {
-    float* slot = red[py][cx];
+  dw_fold_atomics<CQ>(red, acc, accb, dw, dbias, blk.bx, C);
+}
+
+// Row walk for dil = 1 (the MixFFN depthwise convolution: forward + GELU, data gradient, fused GELU backward).  A thread owns 4 channels x
+// WR adjacent columns x a BAND of `band` output rows of one image and walks DOWN the band, as dw_dilated_walk does on a sub-lattice: every
+// input row is requested once per run ((WR + 2) / WR loads per output plus the band's two halo rows -- loads only, no output is computed
+// twice -- against 3.75 / 4.5 in the row-run kernels), and the requests run LA rows ahead of the arithmetic, so a thread streams instead
+// of paying one full memory latency per run.  The rows wait AND are used in a ring of LA + 3 raw (for bf16: packed) register rows -- the
+// three rows under the stencil are unpacked where they are used, which is what lets the fused mode's 40 gradient sums fit beside the
+// window at two waves per SIMD.  The band height is the launch's knob between stream length and grid size (launch_walk below).  Tap
+// order and epilogues are dw_stencil_kernel's / dw_gelu_bwd_fused_kernel's, so y, dz and dx are bit-identical to theirs.
+// MODE 0: y = act(conv(x) + bias); MODE 2: dx (+)= conv^T(dy) (mirrored taps; ACC: += the previous dx); MODE 3: dz = da * gelu'(conv(x)
+// + bias) stored, and acc9 / accb += the thread's share of dw / dbias (from dz before its rounding).
+// columns per thread: 4, and 2 where the registers ask for it -- the fused
+// mode (40 gradient sums beside the window)
+template <int MODE> struct WalkRun { static constexpr int value = MODE == 3 ? 2 : 4; };
+struct WalkGeom {
+  int H, W, band, nbands, rpc;  // nbands = ceil(H / band) bands per image, rpc = ceil(W / WR) runs per row
+  long nthreads;                // B * nbands * rpc
+};
+template <typename T, int MODE, int WR, bool ACC, int LA>
+static __device__ __forceinline__ void dw_walk(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                               const T* __restrict__ da, T* __restrict__ out, const WalkGeom& g, int C, int act,
+                                               int c, unsigned tu, float (&acc9)[9][4], float (&accb)[4]) {
+  constexpr int N = LA + 3;   // ring slots: input row r lives in slot r % N
+  // t -> (b, band, k): k fastest, so the runs of one band sit in the same / the next workgroup
+  const int k0 = (int)(tu % (unsigned)g.rpc) * WR;
+  const unsigned t1 = tu / (unsigned)g.rpc;
+  const int h0 = (int)(t1 % (unsigned)g.nbands) * g.band, b = (int)(t1 / (unsigned)g.nbands);
+  const int nr = min(g.band, g.H - h0);   // output rows h0 .. h0 + nr - 1; input row r <-> image row h0 - 1 + r, r = 0 .. nr + 1
+  // byte offsets from the tensors' bases (the launch keeps the tensor below 4 GiB): one address register per load
+  const unsigned rowb = (unsigned)(g.W * C) * (unsigned)sizeof(T);
+  const unsigned img0 = (unsigned)(b * g.H) * rowb;
+  // window column ci <-> image column k0 - 1 + ci (W is a multiple of WR: only the two halo columns can lie outside the image; they read
+  // a clamped address and are zeroed when the row is first used)
+  const bool cok_l = k0 > 0, cok_r = k0 + WR < g.W;
+  unsigned coff[WR + 2];
 #pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) slot[t * 4 + j] = acc[t][j];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) slot[36 + j] = accb[j];
+  for (int ci = 0; ci < WR + 2; ++ci) {
+    const int kc = k0 - 1 + ci;
+    coff[ci] = (unsigned)((kc >= 0 && kc < g.W ? kc : k0) * C + c) * (unsigned)sizeof(T);
   }
-  __syncthreads();
-  for (int k = threadIdx.x; k < CQ * 40; k += blockDim.x) {
-    const int gx = k / 40, v = k - gx * 40;
-    const int cc = (blk.bx * CQ + gx) * 4;
-    if (cc >= C) continue;
-    float s = 0.f;
+  float wr[9][4], bs[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int l = 0; l < RL; ++l) s += red[l][gx][v];
-    if (v < 36) {
-      const int t = v >> 2, j = v & 3;
-      atomicAdd(dw + (cc + j) * 9 + t, s);
-    } else if (dbias) {
-      atomicAdd(dbias + cc + (v - 36), s);
+  for (int tp = 0; tp < 9; ++tp) ld4(w + (MODE == 2 ? 8 - tp : tp) * C + c, wr[tp]);
+  if (MODE != 2 && bias) ld4(bias + c, bs);
+
+  constexpr bool has_side = MODE == 3 || (MODE == 2 && ACC);
+  constexpr int SW = has_side ? WR : 1;
+  Raw<T> raw[N][WR + 2];   // input rows
+  Raw<T> sraw[N][SW];      // side row of output row r - 2, needed when input row r is: da (MODE 3) / the previous dx (ACC)
+  const char* xb = reinterpret_cast<const char*>(x);
+  const char* sb = reinterpret_cast<const char*>(MODE == 3 ? da : out);
+  char* ob = reinterpret_cast<char*>(out);
+  // Every request issues the same loads and nothing in the loop below is conditional but its exit, so the compiler can COUNT the loads
+  // in flight (s_waitcnt vmcnt(n)) instead of draining them: a request past the band's last input row repeats that row (cache hits),
+  // and one outside the image reads a clamped row that zero_pad discards.  (No select on the loaded value here: it would pin the
+  // wait for the data right behind the request.)
+  auto request = [&](int r, Raw<T> (&dst)[WR + 2], Raw<T> (&sdst)[SW]) {
+    const int ih = h0 - 1 + min(r, nr + 1);
+    const unsigned rb = img0 + (unsigned)min(max(ih, 0), g.H - 1) * rowb;
+#pragma unroll
+    for (int ci = 0; ci < WR + 2; ++ci) dst[ci].load(reinterpret_cast<const T*>(xb + (rb + coff[ci])), true);
+    if (has_side) {
+      const unsigned srb = img0 + (unsigned)(h0 + min(max(r - 2, 0), nr - 1)) * rowb;
+#pragma unroll
+      for (int i = 0; i < SW; ++i) sdst[i].load(reinterpret_cast<const T*>(sb + (srb + coff[i + 1])), true);
     }
+  };
+  auto zero_pad = [&](int r, Raw<T> (&row)[WR + 2]) {   // rows / columns outside the image = zero padding
+    const bool ok = (unsigned)(h0 - 1 + r) < (unsigned)g.H;
+    row[0].keep(ok && cok_l);
+#pragma unroll
+    for (int ci = 1; ci <= WR; ++ci) row[ci].keep(ok);
+    row[WR + 1].keep(ok && cok_r);
+  };
+#pragma unroll
+  for (int r = 0; r < N; ++r) request(r, raw[r], sraw[r]);
+  zero_pad(0, raw[0]);
+  zero_pad(1, raw[1]);
+  for (int j0 = 0; j0 < nr; j0 += N) {
+#pragma unroll
+    for (int s = 0; s < N; ++s) {   // output row j = j0 + s: input rows j, j + 1, j + 2 live in slots s, s + 1, s + 2 (mod N)
+      const int j = j0 + s;
+      const bool live = j < nr;   // a band's last pass may run past its end: those rows load (clamped), compute and are dropped
+      zero_pad(j + 2, raw[(s + 2) % N]);
+#pragma unroll
+      for (int ci = 0; ci < WR + 2; ++ci) {
+        raw[s][ci].pin();
+        raw[(s + 1) % N][ci].pin();
+      }
+      const unsigned orb = img0 + (unsigned)(h0 + j) * rowb;
+      float win[3][3][4];  // [column slot][kh][channel]
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh) {
+        raw[(s + kh) % N][0].unpack(win[0][kh]);
+        raw[(s + kh) % N][1].unpack(win[1][kh]);
+      }
+#pragma unroll
+      for (int i = 0; i < WR; ++i) {
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh) raw[(s + kh) % N][i + 2].unpack(win[(i + 2) % 3][kh]);
+        float acc[4] = {bs[0], bs[1], bs[2], bs[3]};
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+          for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] = tap<T>(win[(i + kw) % 3][kh][q], wr[kh * 3 + kw][q], acc[q]);
+        float sd[4] = {0.f, 0.f, 0.f, 0.f};
+        if (has_side) {
+          sraw[(s + 2) % N][has_side ? i : 0].keep(live);
+          sraw[(s + 2) % N][has_side ? i : 0].unpack(sd);
+        }
+        if (MODE == 0) {
+          if (act == 2) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] = gelu_erf(acc[q]);
+          }
+        } else if (MODE == 2) {
+          if (ACC) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q] += sd[q];
+          }
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            acc[q] = sd[q] * gelu_erf_grad(acc[q]);
+            accb[q] += acc[q];
+          }
+#pragma unroll
+          for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+            for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+              for (int q = 0; q < 4; ++q) acc9[kh * 3 + kw][q] += acc[q] * win[(i + kw) % 3][kh][q];
+          // one output at a time: left alone, the compiler interleaves the WR outputs' sums and spills the windows they wait for
+#pragma unroll
+          for (int tp = 0; tp < 9; ++tp)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) CMDA_DW_PIN(acc9[tp][q]);
+        }
+        if (live) st4(reinterpret_cast<T*>(ob + (orb + coff[i + 1])), acc);
+      }
+      request(j + N, raw[s], sraw[s]);
+    }
+  }
+}
+
+// block = CQ channel quads x (256 / CQ) run lanes.  MODE 3 ends in dw_fold_atomics, so its threads without work stay for the barrier and
+// it runs 16 quads x 16 run lanes (the fewest atomics per pixel: see dw_gelu_bwd_fused_kernel); the others run 64 x 4 as the dilated walk.
+template <typename T, int MODE, int CQ, int WR, bool ACC, int LA>
+__global__ __launch_bounds__(256, 2) void dw_walk_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
+                                                      const T* __restrict__ da, T* __restrict__ out, float* __restrict__ dw,
+                                                      float* __restrict__ dbias, WalkGeom g, int C, int act, int gx) {
+  constexpr int RL = 256 / CQ;
+  const int cx = threadIdx.x % CQ, py = threadIdx.x / CQ;
+  const BlockXY blk = xcd_block(gx);
+  const int c = (blk.bx * CQ + cx) * 4;
+  const long t = blk.by * RL + py;
+  float acc9[9][4], accb[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int tp = 0; tp < 9; ++tp)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc9[tp][q] = 0.f;
+  if (c < C && t < g.nthreads) dw_walk<T, MODE, WR, ACC, LA>(x, w, bias, da, out, g, C, act, c, (unsigned)t, acc9, accb);
+  if (MODE == 3) {
+    __shared__ float red[RL][CQ][41];
+    dw_fold_atomics<CQ>(red, acc9, accb, dw, dbias, blk.bx, C);
   }
 }
 
 static inline bool too_big(long n) { return n >= (1L << 32); }
 static inline int run_len(int dtype) { return dtype == CMDA_BF16 ? RunLen<bf16_t>::value : RunLen<float>::value; }
+
+// workgroups a walk's grid should keep (2 per CU): the band is the tallest of 16 / 8 / 4 rows that still gives that many (a walk passes
+// over its band four rows at a time)
+constexpr long kWalkMinBlocks = 512;
+// ... and the grid at band 4 below which a walk DECLINES and the row-run kernel runs: a row of a walk costs about a microsecond however
+// few threads walk, so on the small maps the one-shot kernels win (graph-timed at the MiT-B5 stage shapes, batch 2 / 4 / 8,
+// profiles/dw_walk_band_sweep.txt: forward 5.5-5.9 us against 6.8-7.3 at 64-128 workgroups, 10.4 against 11.1 at 320; data gradient
+// 4.3-4.6 against 4.9-5.2 at 64-128 and ahead from 160 on; the fused backward is level or ahead everywhere)
+template <int MODE> struct WalkTakes { static constexpr long blocks = MODE == 0 ? 512 : MODE == 2 ? 256 : 0; };
+constexpr int kWalkDeclined = 1;
+
+// what the walk takes: bf16, dil = 1, whole runs per row (no ragged last run: its stores are unconditional) and 32-bit byte offsets;
+// the rest -- fp32 (parity mode: see tap()), odd widths -- stays with the row-run kernels.  CMDA_DW_BAND=0 sends everything there
+// (A/B switch); n > 0 fixes the band height.
+template <int MODE>
+static inline bool walk_takes(int B, int H, int W, int C, int dil, int dtype, int* band) {
+  const char* e = getenv("CMDA_DW_BAND");
+  *band = e ? atoi(e) : -1;
+  const long bytes = (long)B * H * W * C * 2;
+  return dil == 1 && *band != 0 && dtype == CMDA_BF16 && W % WalkRun<MODE>::value == 0 && bytes < (1L << 32);
+}
+
+template <int MODE, int CQ>
+static int launch_walk(const void* x, const float* w, const float* bias, const void* da, void* out, float* dw, float* dbias, int B, int H,
+                       int W, int C, int act, int accumulate, void* stream, int band) {
+  typedef bf16_t T;
+  constexpr int wrun = WalkRun<MODE>::value;
+  constexpr int rl = 256 / CQ;
+  constexpr int la = 1;   // rows in flight behind the stencil (MODE 3 requests its da row with every x row)
+  const int gx = (C / 4 + CQ - 1) / CQ;
+  WalkGeom g;
+  g.H = H; g.W = W;
+  g.rpc = (W + wrun - 1) / wrun;
+  auto blocks = [&](int bh) { return ((long)B * ((H + bh - 1) / bh) * g.rpc + rl - 1) / rl * gx; };
+  if (band <= 0) {
+    if (blocks(4) < WalkTakes<MODE>::blocks) return kWalkDeclined;
+    band = 16;
+    while (band > 4 && blocks(band) < kWalkMinBlocks) band >>= 1;
+  }
+  g.band = band < H ? band : H;
+  g.nbands = (H + g.band - 1) / g.band;
+  g.nthreads = (long)B * g.nbands * g.rpc;
+  const long nb = blocks(g.band);
+  if (too_big(g.nthreads) || nb > 0x7fffffffL) return CMDA_ERR_SHAPE;
+  if (MODE == 2 && accumulate)
+    CMDA_LAUNCH((dw_walk_kernel<T, MODE, CQ, wrun, MODE == 2, la>), dim3((unsigned)nb), dim3(256), 0, stream, (const T*)x, w, bias,
+                (const T*)da, (T*)out, dw, dbias, g, C, act, gx);
+  else
+    CMDA_LAUNCH((dw_walk_kernel<T, MODE, CQ, wrun, false, la>), dim3((unsigned)nb), dim3(256), 0, stream, (const T*)x, w, bias,
+                (const T*)da, (T*)out, dw, dbias, g, C, act, gx);
+  CMDA_CHECK_LAUNCH();
+}
 
 template <int MODE>
 static int launch_stencil(const void* x, const float* w, const float* bias, const void* da, void* out, int B, int H, int W,
@@ -581,6 +827,13 @@ static int launch_stencil(const void* x, const float* w, const float* bias, cons
     CMDA_CHECK_LAUNCH();
   }
   if (stats) return CMDA_ERR_UNSUPPORTED;   // the fused statistics exist on the dilated walk only
+  if constexpr (MODE != 1) {   // row walk (dw_walk_kernel); the backward prep (no caller in the training step) stays a row-run stencil
+    int band;
+    if (walk_takes<MODE>(B, H, W, C, dil, dtype, &band)) {
+      const int rc = launch_walk<MODE, 64>(x, w, bias, da, out, nullptr, nullptr, B, H, W, C, act, accumulate, stream, band);
+      if (rc != kWalkDeclined) return rc;
+    }
+  }
   const RunGeom g = run_geom(B, H, W, dil, run_len(dtype));
   if (too_big(g.nruns)) return CMDA_ERR_SHAPE;
   const long nblk = (g.nruns + 3) / 4 * gx;
@@ -642,6 +895,11 @@ extern "C" int cmda_dwconv3x3_gelu_bwd_fused(const void* x, const float* w, cons
   const long npix = (long)B * H * W;
   if (npix * C <= 0) return CMDA_OK;
   if ((C & 3) || dil < 1) return CMDA_ERR_SHAPE;
+  int band;
+  if (walk_takes<3>(B, H, W, C, dil, dtype, &band)) {   // row walk
+    const int rc = launch_walk<3, 16>(x, w, bias, da, dz, dw, dbias, B, H, W, C, 2, 0, stream, band);
+    if (rc != kWalkDeclined) return rc;
+  }
   const RunGeom g = run_geom(B, H, W, dil, 4);
   if (too_big(npix) || too_big(g.nruns)) return CMDA_ERR_SHAPE;
   constexpr int cq = 16, rl = 256 / cq;
