@@ -208,9 +208,11 @@ template <int N>
 static inline void dma_wait() { emu::wave_barrier(); }  // emulated lanes are fibers: rendezvous so every lane's copy is done
 #endif
 
-// erf by Abramowitz & Stegun 7.1.26 (|abs error| < 1.5e-7, i.e. fp32 round-off level): ~12 VALU ops instead of the
-// ~40 of libm's erff -- the exact-erf GELU of the reference (nn.GELU, mix_transformer.py:26) stays well inside the parity
-// bound while the MixFFN stencil kernels stop being VALU-bound.
+// erf by Abramowitz & Stegun 7.1.26: ~12 VALU ops instead of the ~40 of libm's erff -- the exact-erf GELU of the reference (nn.GELU,
+// mix_transformer.py:26) stays well inside the parity bound while the MixFFN stencil kernels stop being VALU-bound.  The series is
+// within 1.5e-7 of erf in exact arithmetic; evaluated in fp32 (1 - poly * e rounds near 1) the GELU built on it measures up to
+// 4.4e-7 absolute over z in [-12, 12] (worst at z = 3.17), 2.0 x (0.5 |z| 1.5e-7 + 2^-24 |gelu|), and its derivative 2.1e-7:
+// tests/test_row_statistics.py::test_gelu_range_* holds both to 4 x the measured ratios.
 #ifdef CMDA_EMU
 static inline float fast_rcp(float x) { return 1.0f / x; }
 #else

@@ -51,14 +51,22 @@ def test_product_has_no_cpu_fallback():
 # only inside a full model).  A new entry point fails test_every_entry_point_has_a_kernel_level_test until its test exists and is
 # listed here.  Queries map to the test that asserts their value.
 _K, _G, _O, _P, _F, _I = 'test_kernels.py', 'test_gemm.py', 'test_optim.py', 'test_pipeline.py', 'test_fdist.py', 'test_image_uda.py'
+_R = 'test_row_statistics.py'
 KERNEL_TESTS = {
     'cmda_abi_version': ['test_abi.py::test_header_symbols_exported_by_hip_library'],
     'cmda_adamw_step': [f'{_O}::test_adamw_step_stream', f'{_K}::test_classmix_ema_adamw'],
-    'cmda_attention_bwd': [f'{_K}::test_fused_attention'],
-    'cmda_attention_bwd_direct': [f'{_K}::test_fused_attention'],
-    'cmda_attention_bwd_x3': [f'{_K}::test_fused_attention_split_bf16'],
-    'cmda_attention_fwd': [f'{_K}::test_fused_attention', f'{_K}::test_fused_attention_eval_keys'],
-    'cmda_attention_fwd_x3': [f'{_K}::test_fused_attention_split_bf16'],
+    'cmda_attention_bwd': [f'{_K}::test_fused_attention', f'{_R}::test_attention_two_pass_blocks', f'{_R}::test_attention_dkv_regimes',
+                           f'{_R}::test_attention_key_slices', f'{_R}::test_attention_one_hot_addressing',
+                           f'{_R}::test_attention_dkv32_accumulates', f'{_R}::test_attention_wide_heads'],
+    'cmda_attention_bwd_direct': [f'{_K}::test_fused_attention', f'{_R}::test_attention_dkv_regimes'],
+    'cmda_attention_bwd_x3': [f'{_K}::test_fused_attention_split_bf16', f'{_R}::test_attention_two_pass_blocks',
+                              f'{_R}::test_attention_dkv_regimes', f'{_R}::test_attention_key_slices',
+                              f'{_R}::test_attention_one_hot_addressing', f'{_R}::test_attention_dkv32_accumulates'],
+    'cmda_attention_fwd': [f'{_K}::test_fused_attention', f'{_K}::test_fused_attention_eval_keys', f'{_R}::test_attention_two_pass_blocks',
+                           f'{_R}::test_attention_key_slices', f'{_R}::test_attention_eval_keys_forward',
+                           f'{_R}::test_attention_one_hot_addressing', f'{_R}::test_attention_wide_heads'],
+    'cmda_attention_fwd_x3': [f'{_K}::test_fused_attention_split_bf16', f'{_R}::test_attention_two_pass_blocks',
+                              f'{_R}::test_attention_key_slices', f'{_R}::test_attention_one_hot_addressing'],
     'cmda_axpby': [f'{_K}::test_permute_cast_colsum_axpby'],
     'cmda_bilinear_bwd': [f'{_K}::test_bilinear'],
     'cmda_bilinear_fwd': [f'{_K}::test_bilinear'],
@@ -69,8 +77,8 @@ KERNEL_TESTS = {
     'cmda_bn_train_fwd2': [f'{_K}::test_bn_train_fwd2', f'{_K}::test_bn_train_fwd2_epilogue_statistics'],
     'cmda_cast_clear': [f'{_K}::test_cast_clear'],
     'cmda_cast_pad_cols': [f'{_K}::test_rows_fill_cast_pad_nchw_pad'],
-    'cmda_ce_upsample_bwd': [f'{_K}::test_ce_upsample'],
-    'cmda_ce_upsample_fwd': [f'{_K}::test_ce_upsample'],
+    'cmda_ce_upsample_bwd': [f'{_K}::test_ce_upsample', f'{_R}::test_ce_upsample_range'],
+    'cmda_ce_upsample_fwd': [f'{_K}::test_ce_upsample', f'{_R}::test_ce_upsample_range'],
     'cmda_class_mix': [f'{_K}::test_classmix_ema_adamw'],
     'cmda_class_mix_label': [f'{_K}::test_classmix_ema_adamw'],
     'cmda_color_jitter': [f'{_K}::test_strong_augmentation'],
@@ -81,10 +89,10 @@ KERNEL_TESTS = {
     'cmda_crop_flip_resize_f32': [f'{_P}::test_target_pipeline_golden'],
     'cmda_dwconv3x3_bwd_data': [f'{_K}::test_dwconv'],
     'cmda_dwconv3x3_bwd_weight': [f'{_K}::test_dwconv'],
-    'cmda_dwconv3x3_fwd': [f'{_K}::test_dwconv'],
+    'cmda_dwconv3x3_fwd': [f'{_K}::test_dwconv', f'{_R}::test_gelu_range_depthwise'],
     'cmda_dwconv3x3_fwd_stats': [f'{_K}::test_dwconv'],
-    'cmda_dwconv3x3_gelu_bwd_fused': [f'{_K}::test_dwconv'],
-    'cmda_dwconv3x3_gelu_bwd_prep': [f'{_K}::test_dwconv'],
+    'cmda_dwconv3x3_gelu_bwd_fused': [f'{_K}::test_dwconv', f'{_R}::test_gelu_range_depthwise'],
+    'cmda_dwconv3x3_gelu_bwd_prep': [f'{_K}::test_dwconv', f'{_R}::test_gelu_range_depthwise'],
     'cmda_ema_update': [f'{_O}::test_ema_update_stream', f'{_K}::test_classmix_ema_adamw'],
     'cmda_event_prep': [f'{_P}::test_target_pipeline_golden'],
     'cmda_events_norm': [f'{_K}::test_voxel_golden'],
@@ -93,31 +101,33 @@ KERNEL_TESTS = {
     'cmda_fdist_label_mask': [f'{_F}::test_fdist_label_mask_matches_reference'],
     'cmda_gaussian_blur': [f'{_K}::test_strong_augmentation'],
     'cmda_gemm': [f'{_G}::test_gemm_layouts', f'{_G}::test_gemm_batched_heads', f'{_G}::test_conv_implicit_gemm',
-                  f'{_G}::test_gemm_grouped_tile_walk'],
+                  f'{_G}::test_gemm_grouped_tile_walk', f'{_R}::test_gelu_range_gemm_epilogue', f'{_R}::test_attention_unfused_path'],
     'cmda_gemm_grouped': [f'{_G}::test_gemm_deferred_grouped_weight_gradients'],
     'cmda_isr_from_gray': [f'{_K}::test_isr_golden'],
     'cmda_isr_gray': [f'{_K}::test_isr_golden'],
-    'cmda_layernorm_bwd': [f'{_K}::test_layernorm_single_dtype_entry_points'],
+    'cmda_layernorm_bwd': [f'{_K}::test_layernorm_single_dtype_entry_points', f'{_R}::test_layernorm_backward_at_ratio_1000'],
     'cmda_layernorm_bwd2': [f'{_K}::test_layernorm', f'{_K}::test_layernorm_fp32_stream_bf16_operands',
-                            f'{_K}::test_layernorm_deferred_parameter_gradients'],
+                            f'{_K}::test_layernorm_deferred_parameter_gradients', f'{_R}::test_layernorm_backward_at_ratio_1000'],
     'cmda_layernorm_fold_batch': [f'{_K}::test_layernorm_deferred_parameter_gradients'],
-    'cmda_layernorm_fwd': [f'{_K}::test_layernorm_single_dtype_entry_points'],
-    'cmda_layernorm_fwd2': [f'{_K}::test_layernorm', f'{_K}::test_layernorm_fp32_stream_bf16_operands'],
+    'cmda_layernorm_fwd': [f'{_K}::test_layernorm_single_dtype_entry_points', f'{_R}::test_layernorm_conditioning'],
+    'cmda_layernorm_fwd2': [f'{_K}::test_layernorm', f'{_K}::test_layernorm_fp32_stream_bf16_operands', f'{_R}::test_layernorm_conditioning'],
     'cmda_layernorm_slots': [f'{_K}::test_layernorm_single_dtype_entry_points'],
     'cmda_luma_u8': [f'{_P}::test_source_pipeline_golden'],
     'cmda_nchw_to_nhwc_pad': [f'{_K}::test_rows_fill_cast_pad_nchw_pad'],
     'cmda_permute4': [f'{_K}::test_permute_cast_colsum_axpby'],
     'cmda_permute4_batch': [f'{_K}::test_permute4_batch'],
     'cmda_pil_resize_u8': [f'{_P}::test_pil_resize_bit_exact_at_loader_sizes', f'{_P}::test_target_pipeline_golden'],
-    'cmda_pseudo_label': [f'{_K}::test_pseudo_label'],
+    'cmda_pseudo_label': [f'{_K}::test_pseudo_label', f'{_R}::test_pseudo_label_range'],
     'cmda_pseudo_weight': [f'{_K}::test_pseudo_label'],
     'cmda_rows_fill': [f'{_K}::test_rows_fill_cast_pad_nchw_pad'],
     'cmda_sample_scale': [f'{_K}::test_sample_scale'],
-    'cmda_softmax_bwd': [f'{_K}::test_softmax'],
-    'cmda_softmax_fwd': [f'{_K}::test_softmax'],
+    'cmda_softmax_bwd': [f'{_K}::test_softmax', f'{_R}::test_softmax_row_lengths', f'{_R}::test_softmax_grid_stride', f'{_R}::test_softmax_range',
+                         f'{_R}::test_softmax_refuses_rows_longer_than_1024', f'{_R}::test_attention_unfused_path'],
+    'cmda_softmax_fwd': [f'{_K}::test_softmax', f'{_R}::test_softmax_row_lengths', f'{_R}::test_softmax_grid_stride', f'{_R}::test_softmax_range',
+                         f'{_R}::test_softmax_refuses_rows_longer_than_1024', f'{_R}::test_attention_unfused_path'],
     'cmda_split_bf16': [f'{_G}::test_gemm_x3_big_three_launch_path'],
     'cmda_time_residual_u8': [f'{_P}::test_source_pipeline_golden'],
-    'cmda_upsample_logits_nchw': [f'{_K}::test_upsample_logits_nchw'],
+    'cmda_upsample_logits_nchw': [f'{_K}::test_upsample_logits_nchw', f'{_R}::test_upsample_logits_range'],
 }
 
 

@@ -82,7 +82,8 @@ def test_wide_attention(tgt, all_wide, B, N, Nk, heads, hd):
     dkv = torch.zeros(B * Nk, 2 * C, device=tgt.device)
     dq = ops.attention_fused_bwd(qd, kvd, dod, dkv, B, N, Nk, heads, C, scale)
     assert_close(dq, dq_ref, 2e-2, name='wide attention dq')
-    assert_close(dkv, dkv_ref, 2e-2, name='wide attention dkv')
+    assert_close(dkv[:, :C], dkv_ref[:, :C], 2e-2, name='wide attention dk')   # (dK and dV each against its own maximum)
+    assert_close(dkv[:, C:], dkv_ref[:, C:], 2e-2, name='wide attention dv')
 
 
 @pytest.mark.parametrize('B,N,Nk,heads,hd', [(1, 100, 280, 1, 320), (1, 90, 260, 1, 128), (1, 280, 280, 1, 512)])
@@ -124,7 +125,8 @@ def test_wide_attention_padding(tgt, all_wide, B, N, Nk, heads, hd):
     assert torch.isfinite(dkv).all() and (dkv[B * Nk:] == 7.0).all(), 'dK | dV rows'
     assert torch.isfinite(stats).all() and (stats[B * N * heads * 2:] == 7.0).all(), 'stats'
     assert_close(dq[:B * N], dq_ref, 2e-2, name='wide attention dq (ragged)')
-    assert_close(dkv[:B * Nk], dkv_ref, 2e-2, name='wide attention dkv (ragged)')
+    assert_close(dkv[:B * Nk, :C], dkv_ref[:, :C], 2e-2, name='wide attention dk (ragged)')
+    assert_close(dkv[:B * Nk, C:], dkv_ref[:, C:], 2e-2, name='wide attention dv (ragged)')
 
 
 def test_wide_attention_rejects_direct_only(tgt):

@@ -314,10 +314,10 @@ def _attention_ref(q, kv, B, N, Nk, heads, C, scale):
 
 
 @pytest.mark.parametrize('B,N,Nk,heads', [(1, 64, 256, 1), (2, 200, 256, 2), (1, 70, 37, 1), (1, 300, 130, 5), (2, 520, 256, 1),
-                                          (16, 4100, 256, 2)])
+                                          (16, 4100, 256, 2), (64, 130, 20, 8)])
 def test_fused_attention(tgt, B, N, Nk, heads):
-    if B * N > 20000 and tgt.device.type != 'cuda':
-        pytest.skip('the 128-queries-per-block launch shape only occurs on grids far too large for the emulator')
+    if B * N > 20000 and tgt.device.type != 'cuda':   # (the 128-queries-per-block launch runs everywhere at (64, 130, 20, 8): 1024 blocks)
+        pytest.skip('65 600 queries x 256 keys: GPU only (emulator run time)')
     """fused softmax(q k^T) v and its backward (probabilities recomputed in LDS) against autograd on the same bf16 inputs"""
     torch.manual_seed(N + Nk)
     C, scale = heads * 64, 0.125
@@ -332,13 +332,15 @@ def test_fused_attention(tgt, B, N, Nk, heads):
     dkv = torch.zeros(B * Nk, 2 * C, device=tgt.device)
     dq = ops.attention_fused_bwd(qd, kvd, dod, dkv, B, N, Nk, heads, C, scale)   # accumulating form: fp32 workspace + atomics
     assert_close(dq, qr.grad, 2e-2, name='attention dq')
-    assert_close(dkv, kvr.grad, 2e-2, name='attention dkv')
+    assert_close(dkv[:, :C], kvr.grad[:, :C], 2e-2, name='attention dk')   # (dK and dV each against its own maximum)
+    assert_close(dkv[:, C:], kvr.grad[:, C:], 2e-2, name='attention dv')
     assert ops.attention_bwd_direct(B, N, Nk, heads) == (N <= 1024)
     if ops.attention_bwd_direct(B, N, Nk, heads):   # few queries: one block per key slice, dK | dV stored straight as bf16
         dkv16 = torch.full((B * Nk, 2 * C), float('nan'), dtype=torch.bfloat16, device=tgt.device)
         dq2 = ops.attention_fused_bwd(qd, kvd, dod, None, B, N, Nk, heads, C, scale, dkv16=dkv16)
         assert_close(dq2, qr.grad, 2e-2, name='attention dq (direct)')
-        assert_close(dkv16, kvr.grad, 2e-2, name='attention dkv (direct)')
+        assert_close(dkv16[:, :C], kvr.grad[:, :C], 2e-2, name='attention dk (direct)')
+        assert_close(dkv16[:, C:], kvr.grad[:, C:], 2e-2, name='attention dv (direct)')
 
 
 @pytest.mark.parametrize('B,N,Nk,heads', [(1, 64, 256, 1), (2, 200, 256, 2), (1, 70, 37, 1), (1, 300, 130, 5), (2, 1100, 256, 1)])
@@ -362,12 +364,14 @@ def test_fused_attention_split_bf16(tgt, B, N, Nk, heads):
     dkv = torch.zeros(B * Nk, 2 * C, device=tgt.device)
     dq = ops.attention_fused_bwd(qd, kvd, dod, dkv, B, N, Nk, heads, C, scale)   # accumulating form: fp32 atomics
     assert_close(dq, qr.grad, 2e-4, name='split-bf16 attention dq')
-    assert_close(dkv, kvr.grad, 2e-4, name='split-bf16 attention dkv')
+    assert_close(dkv[:, :C], kvr.grad[:, :C], 2e-4, name='split-bf16 attention dk')
+    assert_close(dkv[:, C:], kvr.grad[:, C:], 2e-4, name='split-bf16 attention dv')
     if ops.attention_bwd_direct(B, N, Nk, heads):   # few queries: one block per key slice stores dK | dV (fp32)
         dkv2 = torch.full((B * Nk, 2 * C), float('nan'), device=tgt.device)
         dq2 = ops.attention_fused_bwd(qd, kvd, dod, None, B, N, Nk, heads, C, scale, dkv16=dkv2)
         assert_close(dq2, qr.grad, 2e-4, name='split-bf16 attention dq (direct)')
-        assert_close(dkv2, kvr.grad, 2e-4, name='split-bf16 attention dkv (direct)')
+        assert_close(dkv2[:, :C], kvr.grad[:, :C], 2e-4, name='split-bf16 attention dk (direct)')
+        assert_close(dkv2[:, C:], kvr.grad[:, C:], 2e-4, name='split-bf16 attention dv (direct)')
     # through the block-level composite: runtime.gemm_x3 routes fp32 storage to these kernels; same result as the unfused products
     from cmda_amd import nn as K
     import cmda_amd.runtime as rt
@@ -386,7 +390,8 @@ def test_fused_attention_split_bf16(tgt, B, N, Nk, heads):
         rt.set_gemm_x3(False)
     assert_close(o1, o2, 1e-4, name='fused vs unfused split-bf16 attention')
     assert_close(dq1, dq2, 2e-4, name='fused vs unfused split-bf16 dq')
-    assert_close(dkv1, dkv2, 2e-4, name='fused vs unfused split-bf16 dkv')
+    assert_close(dkv1[:, :C], dkv2[:, :C], 2e-4, name='fused vs unfused split-bf16 dk')
+    assert_close(dkv1[:, C:], dkv2[:, C:], 2e-4, name='fused vs unfused split-bf16 dv')
 
 
 @pytest.mark.parametrize('B,N,Nk,heads', [(1, 1120, 280, 2), (2, 280, 260, 5), (1, 70, 320, 8), (1, 300, 257, 1)])
