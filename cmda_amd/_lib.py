@@ -1,4 +1,4 @@
-"""ctypes binding of libcmda_hip.so (the C ABI declared in include/cmda_hip.h).
+"""ctypes binding of libcmda_hip.so (the C ABI declared in include/cmda_hip.h and its extension include/cmda_hip_ext.h).
 
 The product path has exactly one backend: the gfx950 kernel library built in-tree by
 ``__graft_entry__.build()`` / ``make hip``.  If it is missing, or a tensor is not on the GPU,
@@ -18,6 +18,8 @@ _LIB_PATH = os.environ.get('CMDA_HIP_LIB') or os.path.join(_HERE, 'libcmda_hip.s
 c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_void_p
 
 F32, BF16 = 0, 1
+U8, I64 = 0, 1   # integer label tensors of the extension entry points (CMDAX_U8 / CMDAX_I64)
+ABI_VERSION, ABI_EXT_VERSION = 8, 1
 
 
 class View(ctypes.Structure):
@@ -57,6 +59,12 @@ def _declare(lib):
     lib.cmda_attention_bwd_ws_floats.restype = ctypes.c_int64
     lib.cmda_layernorm_slots.restype = ctypes.c_int
     lib.cmda_gemm_grouped_ws_bytes.restype = ctypes.c_int64
+    # the extension table (include/cmda_hip_ext.h) is versioned on its own
+    if not hasattr(lib, 'cmdax_abi_version'):
+        raise CmdaError('the kernel library lacks the ABI extension (cmdax_*): rebuild it')
+    lib.cmdax_abi_version.restype = ctypes.c_int
+    if lib.cmdax_abi_version() != ABI_EXT_VERSION:
+        raise CmdaError('libcmda_hip.so ABI extension version mismatch')
     return lib
 
 
@@ -70,7 +78,7 @@ def _load():
             '(python -c "import __graft_entry__ as g; g.build()" or `make hip`). '
             'cmda_amd has no CPU fallback.')
     _lib = _declare(ctypes.CDLL(_LIB_PATH))
-    if _lib.cmda_abi_version() != 8:
+    if _lib.cmda_abi_version() != ABI_VERSION:
         raise CmdaError('libcmda_hip.so ABI version mismatch')
     return _lib
 
@@ -133,6 +141,14 @@ def dtype_tag(t):
     if t.dtype == torch.bfloat16:
         return BF16
     raise CmdaError(f'unsupported activation dtype {t.dtype}')
+
+
+def label_tag(t):
+    if t.dtype == torch.uint8:
+        return U8
+    if t.dtype == torch.int64:
+        return I64
+    raise CmdaError(f'unsupported label dtype {t.dtype} (uint8 or int64)')
 
 
 def call(name, *args):

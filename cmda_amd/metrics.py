@@ -63,3 +63,64 @@ def eval_metrics(results, gt_seg_maps, num_classes, ignore_index=255, metrics=('
 def mean_iou(results, gt_seg_maps, num_classes, ignore_index=255, nan_to_num=None, label_map=None, reduce_zero_label=False):
     r = eval_metrics(results, gt_seg_maps, num_classes, ignore_index, ('mIoU',), nan_to_num, label_map, reduce_zero_label)
     return {'aAcc': r['aAcc'], 'mIoU': torch.nanmean(r['IoU']), 'mAcc': torch.nanmean(r['Acc']), 'IoU': r['IoU'], 'Acc': r['Acc']}
+
+
+class ConfusionMeter:
+    """The same score from integer counters that stay on the device: `conf` int64 [num_classes + 1, num_classes], row = label
+    (row `num_classes`: labels out of range but not ignored -- `torch.histc` drops them from the label area while their
+    predictions still count in the predicted area, metrics.py:75-86), column = prediction.  `update` and the fused
+    `ops.seg_predict(..., gt=, conf=meter.conf)` only launch kernels; nothing reaches the host before `compute()`.
+    The four area vectors of `total_intersect_and_union` follow from the matrix exactly (integers below 2^53)."""
+
+    def __init__(self, num_classes, ignore_index=255, device=None):
+        self.num_classes, self.ignore_index = int(num_classes), int(ignore_index)
+        self.conf = torch.zeros(self.num_classes + 1, self.num_classes, dtype=torch.int64, device=device)
+
+    @property
+    def device(self):
+        return self.conf.device
+
+    def _label_tensor(self, t):
+        t = torch.as_tensor(t)
+        if t.dtype not in (torch.uint8, torch.int64):
+            t = t.long()
+        return t.to(self.device).contiguous()
+
+    def update(self, pred, gt):
+        """pred, gt: integer label maps of the same number of pixels (tensors on any device, or numpy)"""
+        from . import ops
+        ops.confusion_update(self._label_tensor(pred), self._label_tensor(gt), self.conf, self.num_classes, self.ignore_index)
+        return self
+
+    def reset(self):
+        self.conf.zero_()
+        return self
+
+    def merge(self, other):
+        assert (other.num_classes, other.ignore_index) == (self.num_classes, self.ignore_index)
+        self.conf += other.conf.to(self.device)
+        return self
+
+    def all_reduce(self, group=None):
+        """one int64 all-reduce of the matrix; nothing without an initialised process group"""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            dist.all_reduce(self.conf, group=group)
+        return self
+
+    def areas(self):
+        """(area_intersect, area_union, area_pred, area_label), float64 [num_classes] on the meter's device"""
+        nc = self.num_classes
+        inter = self.conf[:nc].diagonal().double()
+        pred = self.conf.sum(dim=0).double()
+        label = self.conf[:nc].sum(dim=1).double()
+        return inter, pred + label - inter, pred, label
+
+    def compute(self, nan_to_num=None):
+        """the dict `mean_iou` returns: aAcc, mIoU, mAcc, IoU[C], Acc[C]"""
+        inter, union, _, label = self.areas()
+        out = {'aAcc': inter.sum() / label.sum(), 'IoU': inter / union, 'Acc': inter / label}
+        if nan_to_num is not None:
+            out = {k: torch.nan_to_num(v, nan=float(nan_to_num)) for k, v in out.items()}
+        return {'aAcc': out['aAcc'], 'mIoU': torch.nanmean(out['IoU']), 'mAcc': torch.nanmean(out['Acc']), 'IoU': out['IoU'],
+                'Acc': out['Acc']}

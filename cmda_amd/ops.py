@@ -864,6 +864,55 @@ def upsample_logits_nchw(logits, H, W):
     return out
 
 
+FLIP_NONE, FLIP_HORIZONTAL, FLIP_VERTICAL = 0, 1, 2
+
+
+def _check_conf(conf, nc):
+    if conf.dtype != torch.int64 or conf.numel() != (nc + 1) * nc:
+        raise L.CmdaError(f'conf must be int64 with ({nc} + 1) * {nc} cells, got {conf.dtype} {tuple(conf.shape)}')
+
+
+def seg_predict(logits, H, W, out_hw=None, flip=0, gt=None, conf=None, ignore_index=255, out=None):
+    """The evaluation tail in one launch: fp32 NHWC logits [B,h,w,nc] -> uint8 labels [B,OH,OW] = first arg-max of the logits
+    up-sampled to H x W (the network input), resized to out_hw = (OH, OW) when that differs, flipped back (flip: 0 none,
+    1 horizontal, 2 vertical).  With `gt` (uint8 / int64 [B,OH,OW], un-flipped frame) and `conf` (int64 [(nc+1), nc]) the
+    confusion counters are updated in the same launch: conf[gt or nc][label] += 1 where gt != ignore_index; accumulated, never
+    cleared here.  `out`: an existing uint8 [B,OH,OW] tensor to write into."""
+    check_dev(logits, gt, conf, out)
+    if logits.dtype != torch.float32 or logits.dim() != 4:
+        raise L.CmdaError('seg_predict expects fp32 NHWC logits [B,h,w,nc]')
+    B, h, w, nc = logits.shape
+    OH, OW = (int(out_hw[0]), int(out_hw[1])) if out_hw is not None else (int(H), int(W))
+    if out is None:
+        out = torch.empty(B, max(OH, 0), max(OW, 0), dtype=torch.uint8, device=logits.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, OH, OW):
+        raise L.CmdaError(f'seg_predict: out must be uint8 {(B, OH, OW)}')
+    gt_tag = 0
+    if gt is not None:
+        gt_tag = L.label_tag(gt)
+        if gt.numel() != B * OH * OW:
+            raise L.CmdaError(f'seg_predict: gt has {gt.numel()} labels for {B} x {OH} x {OW} pixels')
+    if conf is not None and 1 <= nc <= 32:
+        _check_conf(conf, nc)
+    call('cmdax_seg_predict', ptr(logits), ptr(out), ptr(gt), c_i32(gt_tag), ptr(conf), c_i32(B), c_i32(h), c_i32(w), c_i32(H),
+         c_i32(W), c_i32(OH), c_i32(OW), c_i32(nc), c_i32(int(flip)), c_i32(ignore_index), stream_of(logits))
+    return out
+
+
+def confusion_update(pred, gt, conf, num_classes, ignore_index=255):
+    """conf (int64 [(nc+1), nc], accumulated) += the confusion counters of the label maps pred / gt (uint8 or int64, the same
+    number of pixels): row = gt (row nc: out of range but not ignored), column = pred; pixels with gt == ignore_index and
+    predictions outside [0, nc) are not counted."""
+    check_dev(pred, gt, conf)
+    if pred.numel() != gt.numel():
+        raise L.CmdaError(f'confusion_update: {pred.numel()} predictions for {gt.numel()} labels')
+    if 1 <= num_classes <= 32:
+        _check_conf(conf, num_classes)
+    call('cmdax_confusion_update', ptr(pred), c_i32(L.label_tag(pred)), ptr(gt), c_i32(L.label_tag(gt)), ptr(conf),
+         c_i64(pred.numel()), c_i32(num_classes), c_i32(ignore_index), stream_of(conf))
+    return conf
+
+
 def copy2d(src, dst, rows, cols, src_ld, dst_ld, src_off=0, dst_off=0):
     check_dev(src, dst)
     es = _ESIZE[src.dtype]

@@ -85,7 +85,7 @@ def broadcast_bn_buffers(model, src=0, group=None):
 
 
 def distributed_evaluate(model, samples, num_classes, ignore_index=255, nan_to_num=None, group=None, predict=None,
-                         label_map=None, reduce_zero_label=False, force=False):
+                         label_map=None, reduce_zero_label=False, force=False, on_device=False):
     """Distributed evaluation of the segmentor: `DistEvalHook._do_evaluate` (mmseg/core/evaluation/eval_hooks.py:86-121) +
     `multi_gpu_test` (mmseg/apis/test.py:216-274) + the dataset's mIoU (`mmseg/core/evaluation/metrics.py:89-125`).
 
@@ -101,13 +101,38 @@ def distributed_evaluate(model, samples, num_classes, ignore_index=255, nan_to_n
     Every rank returns the same dict (aAcc, mIoU, mAcc, IoU[C], Acc[C]).  force: run the collectives even at world size 1 (tests).
 
     samples: a sequence of dicts, the keyword arguments of `simple_test` plus `gt_semantic_seg` (integer label map);
-    predict(model, sample) -> label map replaces the default `model.simple_test(True, **inputs)[0]`."""
+    predict(model, sample) -> label map replaces the default `model.simple_test(True, **inputs)[0]`.
+
+    on_device: nothing leaves the GPU per image -- every rank calls `model.predict(True, gt_semantic_seg=gt, meter=meter, **inputs)`
+    (one fused launch behind the network: labels and the confusion counters of a `metrics.ConfusionMeter`), then ONE int64
+    all-reduce of the (num_classes + 1) x num_classes matrix and one `meter.compute`.  The label remappings stay host-side:
+    `label_map` / `reduce_zero_label` raise with it."""
     from . import metrics
+    if on_device:
+        if label_map or reduce_zero_label:
+            raise ValueError('distributed_evaluate: label_map / reduce_zero_label are host-side remappings; not with on_device=True')
+        if predict is not None:
+            raise ValueError('distributed_evaluate: on_device=True scores through model.predict; not with a predict= hook')
     on = dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or force)
     rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
     broadcast_bn_buffers(model, 0, group)
     was_training = model.training
     model.eval()
+    if on_device:
+        dev = next((p.device for p in model.parameters()), torch.device('cpu'))
+        meter = metrics.ConfusionMeter(num_classes, ignore_index, device=dev)
+        with torch.no_grad():
+            for i in range(rank, len(samples), world):
+                s = dict(samples[i])
+                gt = s.pop('gt_semantic_seg')
+                model.predict(True, gt_semantic_seg=gt, meter=meter, **s)
+        if was_training:
+            model.train()
+        if on:
+            if dist.get_backend(group) != 'nccl':   # (a host-only backend: the matrix meets there)
+                meter.conf = meter.conf.cpu()
+            meter.all_reduce(group)
+        return meter.compute(nan_to_num)
     tot = None
     with torch.no_grad():
         for i in range(rank, len(samples), world):

@@ -63,6 +63,30 @@ def _label_maps(seg):
     return list(seg.argmax(dim=1).cpu().numpy())
 
 
+_FLIP_CODES = {'horizontal': ops.FLIP_HORIZONTAL, 'vertical': ops.FLIP_VERTICAL}
+
+
+def _predict_labels(model, logits, in_hw, img_metas, rescale, gt_semantic_seg, meter):
+    """shared tail of every segmentor's `predict`: low-resolution fp32 NHWC logits -> uint8 device label maps [B,OH,OW] in ONE
+    launch (`ops.seg_predict`: up-sample to the input size, resize to the meta's `ori_shape` when `rescale`, flip back, arg-max
+    -- what `simple_test` computes through full-size logits and a host copy).  With `meter` (metrics.ConfusionMeter) and
+    `gt_semantic_seg` the same launch adds the image's confusion counters to the meter."""
+    mode = (model.test_cfg or {}).get('mode', 'whole')
+    if mode != 'whole':
+        raise NotImplementedError(f"{type(model).__name__}: test_cfg.mode '{mode}' (only 'whole' is implemented)")
+    meta = _first_meta(img_metas)
+    out_hw = tuple(meta['ori_shape'][:2]) if rescale and meta.get('ori_shape') is not None else None
+    flip = ops.FLIP_NONE
+    if meta.get('flip'):
+        assert meta['flip_direction'] in _FLIP_CODES
+        flip = _FLIP_CODES[meta['flip_direction']]
+    H, W = in_hw
+    if meter is None or gt_semantic_seg is None:
+        return ops.seg_predict(logits, H, W, out_hw, flip)
+    gt = meter._label_tensor(gt_semantic_seg)
+    return ops.seg_predict(logits, H, W, out_hw, flip, gt, meter.conf, meter.ignore_index)
+
+
 class _TrainFn(torch.autograd.Function):
     """loss = runner.train_fwd(...); backward(dloss) -> runner.train_bwd(saved, dloss)."""
 
@@ -149,6 +173,19 @@ class EncoderDecoder(nn.Module):
             seg_logit = _resize_logits(seg_logit, meta['ori_shape'])
         return _label_maps(_flip_back(seg_logit, meta))
 
+    def encode_decode_lowres(self, img, events=None, test_cfg=None):
+        """fp32 NHWC logits [B, H/4, W/4, nc]"""
+        with torch.no_grad():
+            feats, _ = self.backbone.fwd(img, save=False)
+            logits, _ = self.decode_head.fwd(feats, img.shape[0])
+        return logits
+
+    def predict(self, rescale=True, gt_semantic_seg=None, meter=None, **kwargs):
+        """`simple_test` without leaving the device (keyword inputs `img`, `img_meta`): uint8 device label maps [B,OH,OW]"""
+        img = kwargs['img']
+        return _predict_labels(self, self.encode_decode_lowres(img), img.shape[2:], kwargs.get('img_meta'), rescale,
+                               gt_semantic_seg, meter)
+
 
 @SEGMENTORS.register_module()
 class EventsEncoderDecoder(EncoderDecoder):
@@ -224,6 +261,16 @@ class EventsEncoderDecoder(EncoderDecoder):
     def simple_test(self, rescale=True, **kwargs):
         """:590-603: per-image label maps (numpy)"""
         return _label_maps(self.inference(rescale, **kwargs))
+
+    def predict(self, rescale=True, gt_semantic_seg=None, meter=None, **kwargs):
+        """`simple_test` without leaving the device (the same keyword inputs, resolved as `whole_inference` does): uint8 device
+        label maps [B,OH,OW]"""
+        img = kwargs['image'] if 'image' in kwargs else kwargs.get('warp_image')
+        if isinstance(img, list):
+            img = img[0]
+        events = None if 'image' in kwargs else kwargs.get('events_vg')
+        return _predict_labels(self, self.encode_decode_lowres(img, events), img.shape[2:], kwargs.get('img_metas'), rescale,
+                               gt_semantic_seg, meter)
 
 
 class _Capture:
@@ -543,3 +590,22 @@ class FusionEncoderDecoder(nn.Module):
     def simple_test(self, rescale=True, **kwargs):
         """encoder_decoder.py:973-984: per-image label maps (numpy)"""
         return _label_maps(self.inference(rescale, **kwargs))
+
+    def predict(self, rescale=True, gt_semantic_seg=None, meter=None, **kwargs):
+        """`simple_test` without leaving the device (the same keyword inputs; the input / output_type / train_type cases resolved
+        as `whole_inference` does): uint8 device label maps [B,OH,OW]"""
+        img = kwargs['warp_image'] if 'warp_image' in kwargs else kwargs['image']
+        test_cfg = kwargs.get('test_cfg') or {'output_type': 'fusion'}
+        if self.train_type in {'cs2dsec_image+events', 'cs2dsec_image+events_together'} and 'events_vg' in kwargs:
+            events = kwargs['events_vg']
+        elif self.train_type == 'cs2dz_image+raw-isr' and test_cfg['output_type'] == 'image_isr':
+            events = kwargs['night_isr']
+        else:
+            events = None
+        if self.train_type == 'cs2dz_image+raw-isr':
+            test_cfg = {'output_type': 'fusion'} if test_cfg['output_type'] == 'image_isr' else {'output_type': 'image'}
+        out = self.encode_decode_lowres(img, events, None, test_cfg)
+        if events is None:   # (encode_decode's rule)
+            test_cfg = {'output_type': 'image'}
+        return _predict_labels(self, out[test_cfg['output_type'] + '_output'], img.shape[2:], kwargs.get('img_metas'), rescale,
+                               gt_semantic_seg, meter)

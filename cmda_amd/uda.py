@@ -193,6 +193,9 @@ class DACS(nn.Module):
     def simple_test(self, rescale=True, **kwargs):
         return self.get_model().simple_test(rescale, **kwargs)
 
+    def predict(self, rescale=True, gt_semantic_seg=None, meter=None, **kwargs):
+        return self.get_model().predict(rescale, gt_semantic_seg=gt_semantic_seg, meter=meter, **kwargs)
+
     def get_imnet_model(self):
         return self.imnet_model
 
