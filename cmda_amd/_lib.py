@@ -1,4 +1,5 @@
-"""ctypes binding of libcmda_hip.so (the C ABI declared in include/cmda_hip.h and its extension include/cmda_hip_ext.h).
+"""ctypes binding of libcmda_hip.so (the C ABI declared in include/cmda_hip.h and its extensions include/cmda_hip_ext.h and
+include/cmda_hip_ext2.h).
 
 The product path has exactly one backend: the gfx950 kernel library built in-tree by
 ``__graft_entry__.build()`` / ``make hip``.  If it is missing, or a tensor is not on the GPU,
@@ -20,6 +21,7 @@ c_i32, c_i64, c_f32, c_vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctyp
 F32, BF16 = 0, 1
 U8, I64 = 0, 1   # integer label tensors of the extension entry points (CMDAX_U8 / CMDAX_I64)
 ABI_VERSION, ABI_EXT_VERSION = 8, 1
+ABI_EXT2_VERSION = 1
 
 
 class View(ctypes.Structure):
@@ -65,6 +67,12 @@ def _declare(lib):
     lib.cmdax_abi_version.restype = ctypes.c_int
     if lib.cmdax_abi_version() != ABI_EXT_VERSION:
         raise CmdaError('libcmda_hip.so ABI extension version mismatch')
+    # the second table (include/cmda_hip_ext2.h), again on its own
+    if not hasattr(lib, 'cmdax2_abi_version'):
+        raise CmdaError('the kernel library lacks the second ABI table (cmdax2_*): rebuild it')
+    lib.cmdax2_abi_version.restype = ctypes.c_int
+    if lib.cmdax2_abi_version() != ABI_EXT2_VERSION:
+        raise CmdaError('libcmda_hip.so second ABI table (cmdax2_*) version mismatch')
     return lib
 
 

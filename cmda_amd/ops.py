@@ -913,6 +913,97 @@ def confusion_update(pred, gt, conf, num_classes, ignore_index=255):
     return conf
 
 
+SCORES_LABELS, SCORES_PROBS = 0, 1   # cmdax2_seg_scores `mode`
+
+
+def slide_windows(H, W, crop, stride):
+    """The reference's sliding-window grid (encoder_decoder.py:183-196): the list of (y1, x1, y2, x2), rows of windows outermost;
+    a window the border would cut is shifted back, so every window has the size min(crop, image)."""
+    (H, W), (ch, cw), (sh, sw) = (int(H), int(W)), (int(crop[0]), int(crop[1])), (int(stride[0]), int(stride[1]))
+    if min(H, W, ch, cw, sh, sw) < 1:
+        raise L.CmdaError(f'slide_windows: sizes, crop and stride must be at least 1, got {(H, W)}, {(ch, cw)}, {(sh, sw)}')
+    out = []
+    for i in range(max(H - ch + sh - 1, 0) // sh + 1):
+        for j in range(max(W - cw + sw - 1, 0) // sw + 1):
+            y2, x2 = min(i * sh + ch, H), min(j * sw + cw, W)
+            out.append((max(y2 - ch, 0), max(x2 - cw, 0), y2, x2))
+    return out
+
+
+def _window_args(name, logits, H, W, crop, stride, out_hw):
+    """shared argument checks of the two window ops: (K, B, hl, wl, nc, OH, OW, the six grid scalars as c_i32)"""
+    if logits.dtype != torch.float32 or logits.dim() != 5:
+        raise L.CmdaError(f'{name} expects fp32 NHWC logits of all windows [K,B,hl,wl,nc]')
+    K, B, hl, wl, nc = logits.shape
+    (ch, cw), (sh, sw) = (int(crop[0]), int(crop[1])), (int(stride[0]), int(stride[1]))
+    if min(int(H), int(W), ch, cw, sh, sw) >= 1:   # (anything below 1 is the kernel library's refusal)
+        want = (max(H - ch + sh - 1, 0) // sh + 1) * (max(W - cw + sw - 1, 0) // sw + 1)
+        if K != want:
+            raise L.CmdaError(f'{name}: {K} windows given, the grid of crop {(ch, cw)} / stride {(sh, sw)} on {(H, W)} has {want}')
+    OH, OW = (int(out_hw[0]), int(out_hw[1])) if out_hw is not None else (int(H), int(W))
+    grid = [c_i32(int(v)) for v in (H, W, ch, cw, sh, sw)]
+    return K, B, hl, wl, nc, OH, OW, grid
+
+
+def seg_predict_windows(logits, H, W, crop, stride, out_hw=None, flip=0, gt=None, conf=None, ignore_index=255, out=None):
+    """The evaluation tail of test_cfg.mode 'slide' in one launch: fp32 NHWC logits of all windows [K,B,hl,wl,nc] (window order of
+    `slide_windows(H, W, crop, stride)`) -> uint8 labels [B,OH,OW] = first arg-max of (the sum over the covering windows of the
+    logits up-sampled to the window size) / (their number), resized to out_hw = (OH, OW) when that differs from (H, W), flipped
+    back.  `flip`, `gt`, `conf`, `ignore_index`, `out`: as `seg_predict`, whose result this is when one window covers the image."""
+    check_dev(logits, gt, conf, out)
+    K, B, hl, wl, nc, OH, OW, grid = _window_args('seg_predict_windows', logits, H, W, crop, stride, out_hw)
+    if out is None:
+        out = torch.empty(B, max(OH, 0), max(OW, 0), dtype=torch.uint8, device=logits.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, OH, OW):
+        raise L.CmdaError(f'seg_predict_windows: out must be uint8 {(B, OH, OW)}')
+    gt_tag = 0
+    if gt is not None:
+        gt_tag = L.label_tag(gt)
+        if gt.numel() != B * OH * OW:
+            raise L.CmdaError(f'seg_predict_windows: gt has {gt.numel()} labels for {B} x {OH} x {OW} pixels')
+    if conf is not None and 1 <= nc <= 32:
+        _check_conf(conf, nc)
+    call('cmdax2_seg_scores', ptr(logits), c_i32(SCORES_LABELS), ptr(out), None, c_i32(0), ptr(gt), c_i32(gt_tag), ptr(conf), c_i32(B),
+         c_i32(hl), c_i32(wl), *grid, c_i32(OH), c_i32(OW), c_i32(nc), c_i32(int(flip)), c_i32(ignore_index), stream_of(logits))
+    return out
+
+
+def seg_prob_accumulate(logits, H, W, crop, stride, out_hw, flip, acc, accumulate):
+    """One view of the multi-view test in one launch: acc (fp32 NCHW [B,nc,OH,OW]) = (acc if accumulate else 0) + soft-max over
+    the classes of the view's scores at out_hw = (OH, OW), flipped back -- scores as in `seg_predict_windows` (test_cfg.mode
+    'whole' is the grid of one window: crop = stride = (H, W) and logits [1,B,hl,wl,nc])."""
+    check_dev(logits, acc)
+    K, B, hl, wl, nc, OH, OW, grid = _window_args('seg_prob_accumulate', logits, H, W, crop, stride, out_hw)
+    if acc.dtype != torch.float32 or tuple(acc.shape) != (B, nc, OH, OW):
+        raise L.CmdaError(f'seg_prob_accumulate: acc must be fp32 {(B, nc, OH, OW)}, got {acc.dtype} {tuple(acc.shape)}')
+    call('cmdax2_seg_scores', ptr(logits), c_i32(SCORES_PROBS), None, ptr(acc), c_i32(int(bool(accumulate))), None, c_i32(0), None,
+         c_i32(B), c_i32(hl), c_i32(wl), *grid, c_i32(OH), c_i32(OW), c_i32(nc), c_i32(int(flip)), c_i32(255), stream_of(logits))
+    return acc
+
+
+def prob_predict(acc, n, gt=None, conf=None, ignore_index=255, out=None):
+    """The end of the multi-view test in one launch: summed probabilities of n views (fp32 NCHW [B,nc,OH,OW]) -> uint8 labels
+    [B,OH,OW] = first arg-max of acc / n; `gt`, `conf`, `ignore_index`, `out`: as `seg_predict`."""
+    check_dev(acc, gt, conf, out)
+    if acc.dtype != torch.float32 or acc.dim() != 4:
+        raise L.CmdaError('prob_predict expects fp32 NCHW probabilities [B,nc,OH,OW]')
+    B, nc, OH, OW = acc.shape
+    if out is None:
+        out = torch.empty(B, OH, OW, dtype=torch.uint8, device=acc.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, OH, OW):
+        raise L.CmdaError(f'prob_predict: out must be uint8 {(B, OH, OW)}')
+    gt_tag = 0
+    if gt is not None:
+        gt_tag = L.label_tag(gt)
+        if gt.numel() != B * OH * OW:
+            raise L.CmdaError(f'prob_predict: gt has {gt.numel()} labels for {B} x {OH} x {OW} pixels')
+    if conf is not None and 1 <= nc <= 32:
+        _check_conf(conf, nc)
+    call('cmdax2_prob_predict', ptr(acc), ptr(out), ptr(gt), c_i32(gt_tag), ptr(conf), c_i32(B), c_i32(OH), c_i32(OW), c_i32(nc),
+         c_i32(int(n)), c_i32(ignore_index), stream_of(acc))
+    return out
+
+
 def copy2d(src, dst, rows, cols, src_ld, dst_ld, src_off=0, dst_off=0):
     check_dev(src, dst)
     es = _ESIZE[src.dtype]

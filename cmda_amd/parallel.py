@@ -105,8 +105,10 @@ def distributed_evaluate(model, samples, num_classes, ignore_index=255, nan_to_n
 
     on_device: nothing leaves the GPU per image -- every rank calls `model.predict(True, gt_semantic_seg=gt, meter=meter, **inputs)`
     (one fused launch behind the network: labels and the confusion counters of a `metrics.ConfusionMeter`), then ONE int64
-    all-reduce of the (num_classes + 1) x num_classes matrix and one `meter.compute`.  The label remappings stay host-side:
-    `label_map` / `reduce_zero_label` raise with it."""
+    all-reduce of the (num_classes + 1) x num_classes matrix and one `meter.compute`.  A sample that carries `augs` (a list of
+    keyword dicts, one per view of a multi-scale / flip test) instead of inputs is scored through
+    `model.predict_aug(augs, gt_semantic_seg=gt, meter=meter)`; test_cfg.mode 'slide' needs nothing here, it arrives through
+    `predict`.  The label remappings stay host-side: `label_map` / `reduce_zero_label` raise with it."""
     from . import metrics
     if on_device:
         if label_map or reduce_zero_label:
@@ -125,7 +127,10 @@ def distributed_evaluate(model, samples, num_classes, ignore_index=255, nan_to_n
             for i in range(rank, len(samples), world):
                 s = dict(samples[i])
                 gt = s.pop('gt_semantic_seg')
-                model.predict(True, gt_semantic_seg=gt, meter=meter, **s)
+                if 'augs' in s:      # the views of a multi-scale / flip test: one launch per view and one behind them
+                    model.predict_aug(s['augs'], gt_semantic_seg=gt, meter=meter)
+                else:
+                    model.predict(True, gt_semantic_seg=gt, meter=meter, **s)
         if was_training:
             model.train()
         if on:

@@ -66,25 +66,118 @@ def _label_maps(seg):
 _FLIP_CODES = {'horizontal': ops.FLIP_HORIZONTAL, 'vertical': ops.FLIP_VERTICAL}
 
 
-def _predict_labels(model, logits, in_hw, img_metas, rescale, gt_semantic_seg, meter):
-    """shared tail of every segmentor's `predict`: low-resolution fp32 NHWC logits -> uint8 device label maps [B,OH,OW] in ONE
-    launch (`ops.seg_predict`: up-sample to the input size, resize to the meta's `ori_shape` when `rescale`, flip back, arg-max
-    -- what `simple_test` computes through full-size logits and a host copy).  With `meter` (metrics.ConfusionMeter) and
-    `gt_semantic_seg` the same launch adds the image's confusion counters to the meter."""
-    mode = (model.test_cfg or {}).get('mode', 'whole')
-    if mode != 'whole':
-        raise NotImplementedError(f"{type(model).__name__}: test_cfg.mode '{mode}' (only 'whole' is implemented)")
-    meta = _first_meta(img_metas)
+def _slide_cfg(model):
+    """None under test_cfg.mode 'whole'; (crop_size, stride) under test_cfg = dict(mode='slide', crop_size=(h, w), stride=(h, w))"""
+    cfg = model.test_cfg or {}
+    mode = cfg.get('mode', 'whole')
+    if mode == 'whole':
+        return None
+    if mode != 'slide':
+        raise NotImplementedError(f"{type(model).__name__}: test_cfg.mode '{mode}' (only 'whole' and 'slide' are implemented)")
+    crop, stride = cfg.get('crop_size'), cfg.get('stride')
+    if crop is None or stride is None:
+        raise NotImplementedError(f"{type(model).__name__}: test_cfg.mode 'slide' needs crop_size=(h, w) and stride=(h, w)")
+    return (int(crop[0]), int(crop[1])), (int(stride[0]), int(stride[1]))
+
+
+def _flip_code(meta):
+    if not meta.get('flip'):
+        return ops.FLIP_NONE
+    assert meta['flip_direction'] in _FLIP_CODES
+    return _FLIP_CODES[meta['flip_direction']]
+
+
+def _window_logits(model, spatial, run, crop, stride):
+    """Low-resolution logits of every window of the grid, fp32 NHWC [K,B,hl,wl,nc] (window order of `ops.slide_windows`).  Every
+    spatial input of the sample (`spatial`: name -> NCHW tensor, all of one size) is cropped with the same window and the windows
+    go through the network (`run(spatial) -> fp32 NHWC logits`) as ONE batch of K*B samples, window-major, where the reference
+    loops over them (encoder_decoder.py:190-204).  `model.slide_batch` caps the windows per pass (None: all; 1: the reference's
+    loop)."""
+    B, _, H, W = next(iter(spatial.values())).shape
+    wins = ops.slide_windows(H, W, crop, stride)
+    per = getattr(model, 'slide_batch', None) or len(wins)
+    parts = []
+    for first in range(0, len(wins), per):
+        chunk = wins[first:first + per]
+        batch = {k: torch.cat([t[:, :, y1:y2, x1:x2] for y1, x1, y2, x2 in chunk]).contiguous() for k, t in spatial.items()}
+        logits = run(batch)
+        parts.append(logits.reshape((len(chunk), B) + tuple(logits.shape[1:])))
+    return wins, (parts[0] if len(parts) == 1 else torch.cat(parts))
+
+
+def _slide_inference(model, spatial, run, meta, rescale):
+    """the reference's slide_inference (encoder_decoder.py:175-218) restated with full-size tensors, the path `inference` and
+    `simple_test` take: NCHW logits = (sum over the windows, in order, of the window's logits up-sampled to the window and
+    zero-padded to the image) / (the number of windows per pixel), resized to meta['ori_shape'] when `rescale`"""
+    crop, stride = _slide_cfg(model)
+    wins, logits = _window_logits(model, spatial, run, crop, stride)
+    _, B, _, _, nc = logits.shape
+    H, W = next(iter(spatial.values())).shape[2:]
+    preds = torch.zeros(B, nc, H, W, dtype=torch.float32, device=logits.device)
+    count = torch.zeros(B, 1, H, W, dtype=torch.float32, device=logits.device)
+    for k, (y1, x1, y2, x2) in enumerate(wins):
+        preds += nn.functional.pad(ops.upsample_logits_nchw(logits[k], y2 - y1, x2 - x1), (x1, W - x2, y1, H - y2))
+        count[:, :, y1:y2, x1:x2] += 1
+    preds = preds / count
+    if rescale and meta.get('ori_shape') is not None:
+        preds = _resize_logits(preds, meta['ori_shape'])
+    return preds
+
+
+def _view_logits(model, spatial, run):
+    """one view's window logits [K,B,hl,wl,nc] with their grid (H, W, crop, stride); 'whole' is the grid of one window"""
+    H, W = next(iter(spatial.values())).shape[2:]
+    slide = _slide_cfg(model)
+    if slide is None:
+        return run(spatial)[None], H, W, (H, W), (H, W)
+    return _window_logits(model, spatial, run, *slide)[1], H, W, slide[0], slide[1]
+
+
+def _predict_labels(model, spatial, run, meta, rescale, gt_semantic_seg, meter):
+    """shared tail of every segmentor's `predict`: uint8 device label maps [B,OH,OW] in ONE launch behind the network.
+    'whole': `ops.seg_predict` on the low-resolution fp32 NHWC logits `run(spatial)` (up-sample to the input size, resize to the
+    meta's `ori_shape` when `rescale`, flip back, arg-max -- what `simple_test` computes through full-size logits and a host copy).
+    'slide': the windows as one batch (`_window_logits`), then `ops.seg_predict_windows` (window sum, divide, resize, flip back,
+    arg-max; no nc x H x W tensor per window or per image).  With `meter` (metrics.ConfusionMeter) and `gt_semantic_seg` the same
+    launch adds the image's confusion counters to the meter."""
+    slide = _slide_cfg(model)
     out_hw = tuple(meta['ori_shape'][:2]) if rescale and meta.get('ori_shape') is not None else None
-    flip = ops.FLIP_NONE
-    if meta.get('flip'):
-        assert meta['flip_direction'] in _FLIP_CODES
-        flip = _FLIP_CODES[meta['flip_direction']]
-    H, W = in_hw
+    flip = _flip_code(meta)
+    H, W = next(iter(spatial.values())).shape[2:]
+    score = () if meter is None or gt_semantic_seg is None else (meter._label_tensor(gt_semantic_seg), meter.conf, meter.ignore_index)
+    if slide is None:
+        return ops.seg_predict(run(spatial), H, W, out_hw, flip, *score)
+    logits = _window_logits(model, spatial, run, *slide)[1]
+    return ops.seg_predict_windows(logits, H, W, slide[0], slide[1], out_hw, flip, *score)
+
+
+def _predict_aug(model, views, gt_semantic_seg, meter):
+    """shared body of every segmentor's `predict_aug`: `aug_test` without leaving the device.  views: [(spatial, run, meta)].  One
+    `ops.seg_prob_accumulate` launch per view (the view's soft-max at `ori_shape`, flipped back, written to / added into ONE fp32
+    [B,nc,OH,OW] accumulator; whole or slide mode), then one `ops.prob_predict` launch (divide by the number of views, arg-max,
+    and the confusion counters when `meter` and `gt_semantic_seg` are given)."""
+    assert len(views) >= 1
+    out_hw = tuple(views[0][2]['ori_shape'][:2])
+    acc = None
+    for i, (spatial, run, meta) in enumerate(views):
+        assert tuple(meta['ori_shape'][:2]) == out_hw, 'the views of one image share its ori_shape'
+        logits, H, W, crop, stride = _view_logits(model, spatial, run)
+        if acc is None:
+            acc = torch.empty((logits.shape[1], logits.shape[4]) + out_hw, dtype=torch.float32, device=logits.device)
+        ops.seg_prob_accumulate(logits, H, W, crop, stride, out_hw, _flip_code(meta), acc, i > 0)
     if meter is None or gt_semantic_seg is None:
-        return ops.seg_predict(logits, H, W, out_hw, flip)
-    gt = meter._label_tensor(gt_semantic_seg)
-    return ops.seg_predict(logits, H, W, out_hw, flip, gt, meter.conf, meter.ignore_index)
+        return ops.prob_predict(acc, len(views))
+    return ops.prob_predict(acc, len(views), meter._label_tensor(gt_semantic_seg), meter.conf, meter.ignore_index)
+
+
+def _aug_labels(probs):
+    """the end of the reference's aug_test (encoder_decoder.py:295-304): the views' probabilities summed in order, divided by their
+    number, arg-max; per-image label maps (numpy)"""
+    seg = probs[0]
+    for p in probs[1:]:
+        seg += p
+    seg /= len(probs)
+    return _label_maps(seg)
 
 
 class _TrainFn(torch.autograd.Function):
@@ -163,15 +256,43 @@ class EncoderDecoder(nn.Module):
             logits, _ = self.decode_head.fwd(feats, B)
             return ops.upsample_logits_nchw(logits, H, W)
 
-    def simple_test(self, img, img_meta=None, rescale=True):
-        """encoder_decoder.py:222-285 with test_cfg mode 'whole': logits at the input size, resized to img_meta['ori_shape'] when
-        `rescale`, flipped back when the test pipeline flipped; per-image label maps (numpy) -- the reference's soft-max before
-        the argmax is monotone and skipped."""
+    slide_batch = None   # test_cfg.mode 'slide': windows per network pass (None: all windows of an image as one batch)
+
+    def _test_inputs(self, **kwargs):
+        """(spatial inputs to crop per window, run(spatial) -> low-resolution fp32 NHWC logits, the image's meta)"""
+        return {'img': kwargs['img']}, (lambda s: self.encode_decode_lowres(s['img'])), _first_meta(kwargs.get('img_meta'))
+
+    def slide_inference(self, img, img_meta=None, rescale=True):
+        """encoder_decoder.py:175-218 (test_cfg = dict(mode='slide', crop_size=(h, w), stride=(h, w))): NCHW logits of the image
+        from its overlapping windows, averaged where they overlap; at img_meta['ori_shape'] when `rescale`"""
+        spatial, run, meta = self._test_inputs(img=img, img_meta=img_meta)
+        return _slide_inference(self, spatial, run, meta, rescale)
+
+    def _seg_logit(self, img, img_meta, rescale):
+        """slide_inference / whole_inference (:175-237): logits at the input size, resized to img_meta['ori_shape'] when `rescale`"""
+        if _slide_cfg(self) is not None:
+            return self.slide_inference(img, img_meta, rescale)
         seg_logit = self.encode_decode(img, img_meta)
         meta = _first_meta(img_meta)
         if rescale and meta.get('ori_shape') is not None:
             seg_logit = _resize_logits(seg_logit, meta['ori_shape'])
-        return _label_maps(_flip_back(seg_logit, meta))
+        return seg_logit
+
+    def inference(self, img, img_meta=None, rescale=True):
+        """encoder_decoder.py:239-272: soft-max of the logits (whole or slide), flipped back when the test pipeline flipped"""
+        return _flip_back(torch.softmax(self._seg_logit(img, img_meta, rescale), dim=1), _first_meta(img_meta))
+
+    def simple_test(self, img, img_meta=None, rescale=True):
+        """encoder_decoder.py:222-285: logits at the input size (test_cfg mode 'whole', or 'slide' from overlapping windows),
+        resized to img_meta['ori_shape'] when `rescale`, flipped back when the test pipeline flipped; per-image label maps (numpy)
+        -- the reference's soft-max before the argmax is monotone and skipped."""
+        return _label_maps(_flip_back(self._seg_logit(img, img_meta, rescale), _first_meta(img_meta)))
+
+    def aug_test(self, imgs, img_metas, rescale=True):
+        """encoder_decoder.py:287-304: the views' `inference` outputs (multi-scale / flipped inputs, all rescaled to the image's
+        ori_shape) averaged, arg-max; per-image label maps (numpy).  Only rescale=True, as in the reference."""
+        assert rescale
+        return _aug_labels([self.inference(img, meta, rescale) for img, meta in zip(imgs, img_metas)])
 
     def encode_decode_lowres(self, img, events=None, test_cfg=None):
         """fp32 NHWC logits [B, H/4, W/4, nc]"""
@@ -181,10 +302,14 @@ class EncoderDecoder(nn.Module):
         return logits
 
     def predict(self, rescale=True, gt_semantic_seg=None, meter=None, **kwargs):
-        """`simple_test` without leaving the device (keyword inputs `img`, `img_meta`): uint8 device label maps [B,OH,OW]"""
-        img = kwargs['img']
-        return _predict_labels(self, self.encode_decode_lowres(img), img.shape[2:], kwargs.get('img_meta'), rescale,
-                               gt_semantic_seg, meter)
+        """`simple_test` without leaving the device (keyword inputs `img`, `img_meta`; test_cfg mode 'whole' or 'slide'): uint8
+        device label maps [B,OH,OW]"""
+        return _predict_labels(self, *self._test_inputs(**kwargs), rescale, gt_semantic_seg, meter)
+
+    def predict_aug(self, samples, gt_semantic_seg=None, meter=None):
+        """`aug_test` without leaving the device; samples: one keyword dict per view, as `predict` takes them: uint8 device label
+        maps [B,OH,OW] at the views' common ori_shape"""
+        return _predict_aug(self, [self._test_inputs(**kw) for kw in samples], gt_semantic_seg, meter)
 
 
 @SEGMENTORS.register_module()
@@ -250,27 +375,46 @@ class EventsEncoderDecoder(EncoderDecoder):
             seg_logit = _resize_logits(seg_logit, _first_meta(kwargs['img_metas'])['ori_shape'])
         return seg_logit
 
+    def _test_inputs(self, **kwargs):
+        """(spatial inputs to crop per window, run(spatial) -> low-resolution fp32 NHWC logits, the image's meta); the keyword
+        inputs resolved as `whole_inference` does"""
+        img = kwargs['image'] if 'image' in kwargs else kwargs.get('warp_image')
+        if isinstance(img, list):
+            img = img[0]
+        events = None if 'image' in kwargs else kwargs.get('events_vg')
+        spatial = {'img': img} if events is None else {'img': img, 'events': events}
+        return spatial, (lambda s: self.encode_decode_lowres(s['img'], s.get('events'))), _first_meta(kwargs.get('img_metas'))
+
+    def slide_inference(self, rescale, **kwargs):
+        """test_cfg = dict(mode='slide', crop_size=(h, w), stride=(h, w)).  The reference's copy of slide_inference in this class
+        (:480-520) calls encode_decode with the plain class's signature and cannot run; the behaviour is defined by extension of
+        the plain class's (encoder_decoder.py:175-218): every spatial input of the sample (`image` / `warp_image`, `events_vg`)
+        is cropped with the same window, everything else as there."""
+        spatial, run, meta = self._test_inputs(**kwargs)
+        return _slide_inference(self, spatial, run, meta, rescale)
+
     def inference(self, rescale, **kwargs):
-        """:553-588 (test_cfg.mode 'whole'): soft-max of the logits, flipped back when the test pipeline flipped"""
-        mode = (self.test_cfg or {}).get('mode', 'whole')
-        if mode != 'whole':
-            raise NotImplementedError(f"EventsEncoderDecoder: test_cfg.mode '{mode}' (only 'whole' is implemented)")
-        output = torch.softmax(self.whole_inference(rescale, **kwargs), dim=1)
+        """:553-588: soft-max of the logits (test_cfg.mode 'whole' or 'slide'), flipped back when the test pipeline flipped"""
+        slide = _slide_cfg(self) is not None
+        output = torch.softmax(self.slide_inference(rescale, **kwargs) if slide else self.whole_inference(rescale, **kwargs), dim=1)
         return _flip_back(output, _first_meta(kwargs.get('img_metas')))
 
     def simple_test(self, rescale=True, **kwargs):
         """:590-603: per-image label maps (numpy)"""
         return _label_maps(self.inference(rescale, **kwargs))
 
+    def aug_test(self, samples, rescale=True):
+        """Multi-view test; samples: one keyword dict per view, as `simple_test` takes them.  The reference's copy in this class
+        (:605-620) calls `inference` with the plain class's signature and cannot run; defined by extension of the plain class's
+        (encoder_decoder.py:287-304): the views' `inference` outputs averaged, arg-max; per-image label maps (numpy).  Only
+        rescale=True, as in the reference."""
+        assert rescale
+        return _aug_labels([self.inference(rescale, **kw) for kw in samples])
+
     def predict(self, rescale=True, gt_semantic_seg=None, meter=None, **kwargs):
-        """`simple_test` without leaving the device (the same keyword inputs, resolved as `whole_inference` does): uint8 device
-        label maps [B,OH,OW]"""
-        img = kwargs['image'] if 'image' in kwargs else kwargs.get('warp_image')
-        if isinstance(img, list):
-            img = img[0]
-        events = None if 'image' in kwargs else kwargs.get('events_vg')
-        return _predict_labels(self, self.encode_decode_lowres(img, events), img.shape[2:], kwargs.get('img_metas'), rescale,
-                               gt_semantic_seg, meter)
+        """`simple_test` without leaving the device (the same keyword inputs, resolved as `whole_inference` does; test_cfg mode
+        'whole' or 'slide'): uint8 device label maps [B,OH,OW]"""
+        return _predict_labels(self, *self._test_inputs(**kwargs), rescale, gt_semantic_seg, meter)
 
 
 class _Capture:
@@ -565,8 +709,8 @@ class FusionEncoderDecoder(nn.Module):
             return {k: (ops.upsample_logits_nchw(v, H, W) if v is not None else None) for k, v in out.items()}
         return ops.upsample_logits_nchw(out[test_cfg['output_type'] + '_output'], H, W)
 
-    def whole_inference(self, rescale, **kwargs):
-        """encoder_decoder.py:897-936: logits at the input size, resized once more to img_metas['ori_shape'] when `rescale`"""
+    def _resolve_test_inputs(self, kwargs):
+        """(img, events, test_cfg of encode_decode) from the keyword inputs of the test pipeline (encoder_decoder.py:897-930)"""
         img = kwargs['warp_image'] if 'warp_image' in kwargs else kwargs['image']
         test_cfg = kwargs.get('test_cfg') or {'output_type': 'fusion'}
         if self.train_type in {'cs2dsec_image+events', 'cs2dsec_image+events_together'} and 'events_vg' in kwargs:
@@ -577,35 +721,59 @@ class FusionEncoderDecoder(nn.Module):
             events = None
         if self.train_type == 'cs2dz_image+raw-isr':
             test_cfg = {'output_type': 'fusion'} if test_cfg['output_type'] == 'image_isr' else {'output_type': 'image'}
+        return img, events, test_cfg
+
+    def whole_inference(self, rescale, **kwargs):
+        """encoder_decoder.py:897-936: logits at the input size, resized once more to img_metas['ori_shape'] when `rescale`"""
+        img, events, test_cfg = self._resolve_test_inputs(kwargs)
         seg_logit = self.encode_decode(img, events, test_cfg=test_cfg)
         if rescale and kwargs.get('img_metas') is not None:
             seg_logit = _resize_logits(seg_logit, _first_meta(kwargs['img_metas'])['ori_shape'])
         return seg_logit
 
+    slide_batch = None   # test_cfg.mode 'slide': windows per network pass (None: all windows of an image as one batch)
+
+    def _test_inputs(self, **kwargs):
+        """(spatial inputs to crop per window, run(spatial) -> low-resolution fp32 NHWC logits of the selected output, the meta)"""
+        img, events, test_cfg = self._resolve_test_inputs(kwargs)
+        key = ('image' if events is None else test_cfg['output_type']) + '_output'   # (encode_decode's rule)
+        spatial = {'img': img} if events is None else {'img': img, 'events': events}
+        return (spatial, (lambda s: self.encode_decode_lowres(s['img'], s.get('events'), None, test_cfg)[key]),
+                _first_meta(kwargs.get('img_metas')))
+
+    def slide_inference(self, rescale, **kwargs):
+        """test_cfg = dict(mode='slide', crop_size=(h, w), stride=(h, w)).  The reference's copy of slide_inference in this class
+        (:851-894) calls encode_decode with the plain class's signature and cannot run; the behaviour is defined by extension of
+        the plain class's (encoder_decoder.py:175-218): every spatial input of the sample (`image` / `warp_image`, `events_vg`,
+        `night_isr`) is cropped with the same window, everything else as there."""
+        spatial, run, meta = self._test_inputs(**kwargs)
+        return _slide_inference(self, spatial, run, meta, rescale)
+
     def inference(self, rescale, **kwargs):
-        """encoder_decoder.py:938-971 (test_cfg.mode 'whole'): soft-max of the logits, flipped back when the test pipeline flipped"""
-        output = torch.softmax(self.whole_inference(rescale, **kwargs), dim=1)
+        """encoder_decoder.py:938-971: soft-max of the logits (test_cfg.mode 'whole' or 'slide'), flipped back when the test
+        pipeline flipped"""
+        slide = _slide_cfg(self) is not None
+        output = torch.softmax(self.slide_inference(rescale, **kwargs) if slide else self.whole_inference(rescale, **kwargs), dim=1)
         return _flip_back(output, _first_meta(kwargs.get('img_metas')))
 
     def simple_test(self, rescale=True, **kwargs):
         """encoder_decoder.py:973-984: per-image label maps (numpy)"""
         return _label_maps(self.inference(rescale, **kwargs))
 
+    def aug_test(self, samples, rescale=True):
+        """Multi-view test; samples: one keyword dict per view, as `simple_test` takes them.  The reference's copy in this class
+        (:986-1003) calls `inference` with the plain class's signature and cannot run; defined by extension of the plain class's
+        (encoder_decoder.py:287-304): the views' `inference` outputs averaged, arg-max; per-image label maps (numpy).  Only
+        rescale=True, as in the reference."""
+        assert rescale
+        return _aug_labels([self.inference(rescale, **kw) for kw in samples])
+
     def predict(self, rescale=True, gt_semantic_seg=None, meter=None, **kwargs):
         """`simple_test` without leaving the device (the same keyword inputs; the input / output_type / train_type cases resolved
-        as `whole_inference` does): uint8 device label maps [B,OH,OW]"""
-        img = kwargs['warp_image'] if 'warp_image' in kwargs else kwargs['image']
-        test_cfg = kwargs.get('test_cfg') or {'output_type': 'fusion'}
-        if self.train_type in {'cs2dsec_image+events', 'cs2dsec_image+events_together'} and 'events_vg' in kwargs:
-            events = kwargs['events_vg']
-        elif self.train_type == 'cs2dz_image+raw-isr' and test_cfg['output_type'] == 'image_isr':
-            events = kwargs['night_isr']
-        else:
-            events = None
-        if self.train_type == 'cs2dz_image+raw-isr':
-            test_cfg = {'output_type': 'fusion'} if test_cfg['output_type'] == 'image_isr' else {'output_type': 'image'}
-        out = self.encode_decode_lowres(img, events, None, test_cfg)
-        if events is None:   # (encode_decode's rule)
-            test_cfg = {'output_type': 'image'}
-        return _predict_labels(self, out[test_cfg['output_type'] + '_output'], img.shape[2:], kwargs.get('img_metas'), rescale,
-                               gt_semantic_seg, meter)
+        as `whole_inference` does; test_cfg mode 'whole' or 'slide'): uint8 device label maps [B,OH,OW]"""
+        return _predict_labels(self, *self._test_inputs(**kwargs), rescale, gt_semantic_seg, meter)
+
+    def predict_aug(self, samples, gt_semantic_seg=None, meter=None):
+        """`aug_test` without leaving the device; samples: one keyword dict per view: uint8 device label maps [B,OH,OW] at the
+        views' common ori_shape"""
+        return _predict_aug(self, [self._test_inputs(**kw) for kw in samples], gt_semantic_seg, meter)

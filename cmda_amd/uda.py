@@ -196,6 +196,12 @@ class DACS(nn.Module):
     def predict(self, rescale=True, gt_semantic_seg=None, meter=None, **kwargs):
         return self.get_model().predict(rescale, gt_semantic_seg=gt_semantic_seg, meter=meter, **kwargs)
 
+    def aug_test(self, *args, **kwargs):
+        return self.get_model().aug_test(*args, **kwargs)
+
+    def predict_aug(self, samples, gt_semantic_seg=None, meter=None):
+        return self.get_model().predict_aug(samples, gt_semantic_seg=gt_semantic_seg, meter=meter)
+
     def get_imnet_model(self):
         return self.imnet_model
 
