@@ -1,5 +1,5 @@
-"""ctypes binding of libcmda_hip.so (the C ABI declared in include/cmda_hip.h and its extensions include/cmda_hip_ext.h and
-include/cmda_hip_ext2.h).
+"""ctypes binding of libcmda_hip.so (the C ABI declared in include/cmda_hip.h and its extensions include/cmda_hip_ext.h,
+include/cmda_hip_ext2.h and include/cmda_hip_ext3.h).
 
 The product path has exactly one backend: the gfx950 kernel library built in-tree by
 ``__graft_entry__.build()`` / ``make hip``.  If it is missing, or a tensor is not on the GPU,
@@ -22,6 +22,7 @@ F32, BF16 = 0, 1
 U8, I64 = 0, 1   # integer label tensors of the extension entry points (CMDAX_U8 / CMDAX_I64)
 ABI_VERSION, ABI_EXT_VERSION = 8, 1
 ABI_EXT2_VERSION = 1
+ABI_EXT3_VERSION = 1
 
 
 class View(ctypes.Structure):
@@ -73,6 +74,14 @@ def _declare(lib):
     lib.cmdax2_abi_version.restype = ctypes.c_int
     if lib.cmdax2_abi_version() != ABI_EXT2_VERSION:
         raise CmdaError('libcmda_hip.so second ABI table (cmdax2_*) version mismatch')
+    # the third table (include/cmda_hip_ext3.h): the ISR augmentations
+    if not hasattr(lib, 'cmdax3_abi_version'):
+        raise CmdaError('the kernel library lacks the third ABI table (cmdax3_*): rebuild it')
+    lib.cmdax3_abi_version.restype = ctypes.c_int
+    if lib.cmdax3_abi_version() != ABI_EXT3_VERSION:
+        raise CmdaError('libcmda_hip.so third ABI table (cmdax3_*) version mismatch')
+    lib.cmdax3_sky_mask_ws_bytes.restype = ctypes.c_int64
+    lib.cmdax3_sky_mask_ws_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     return lib
 
 

@@ -94,7 +94,11 @@ class CityscapesICDataset(_SyntheticBase):
     """mmseg/datasets/cityscapes_ic.py:23-272 (source domain): outputs ⊆ {'image', 'label', 'img_time_res', 'img_self_res'}.
     resize 2048x1024 -> image_resize_size -> random crop image_crop_size -> random flip; 'img_time_res' = the log-intensity change
     against the previous sequence frame (create_cityscapes_image_change.py:16-35, computed on the fly), 'img_self_res' = ISR of
-    the cropped image (isr_parms / shift_type as in the reference)."""
+    the cropped image (isr_parms / shift_type as in the reference).  `sky_mask` (a directory of noise images or a uint8 [N,H,W] bank
+    of the crop's size) and `isr_noise=True` apply the two ISR augmentations of cityscapes_ic.py:241-261, :303-336 to 'img_self_res' on
+    the device (ops.sky_mask, ops.isr_noise), per sample in the reference's order: sky-mask draws (torch generator), then the blur coin
+    (torch) and random.uniform x 3.  The noise fields come from the kernel's counter-based generator (seed = torch.initial_seed() at
+    construction, offset = the number of batches made so far), not from torch.randn_like."""
 
     def __init__(self, dataset_path='', image_resize_size=(1024, 512), image_crop_size=(512, 512), image_change_range=1,
                  classes=CLASSES, palette=PALETTE, return_GI_or_IC='image_change', isr_shift_pixel=4, enforce_3_channels=True,
@@ -103,8 +107,8 @@ class CityscapesICDataset(_SyntheticBase):
                  synthetic_length=2975, raw_size=(2048, 1024), seed=0, device=None):
         _warn_synthetic(type(self), dataset_path)
         assert image_crop_size[0] <= image_resize_size[0] and image_crop_size[1] <= image_resize_size[1]
-        assert not (isr_noise or isr_cow_mask or high_resolution_isr or shift_3_channel) and random_flare is None and sky_mask is None, \
-            'augmentations that are off in configs/fusion/* are not implemented'
+        assert not (isr_cow_mask or high_resolution_isr or shift_3_channel) and random_flare is None, \
+            'isr_cow_mask, high_resolution_isr, shift_3_channel and random_flare are not implemented'
         assert shift_type in {'all', 'random', 'rightdown'}
         self.image_resize_size, self.image_crop_size = tuple(image_resize_size), tuple(image_crop_size)
         self.outputs, self.CLASSES, self.PALETTE = set(outputs), classes, palette
@@ -112,6 +116,14 @@ class CityscapesICDataset(_SyntheticBase):
         self.shift_type, self.enforce_3_channels = shift_type, enforce_3_channels
         self.length, self.raw_size, self.seed, self.device = synthetic_length, tuple(raw_size), seed, _device(device)
         self.file_path = {'label': [f'synthetic/{i:06d}_gtFine_labelTrainIds.png' for i in range(min(synthetic_length, 4096))]}
+        self.sky_bank = None
+        if sky_mask is not None:
+            self.sky_bank = ops.load_noise_bank(sky_mask).to(self.device)
+            cw, ch = self.image_crop_size
+            if tuple(self.sky_bank.shape[1:]) != (ch, cw):
+                raise ValueError(f'sky_mask: the noise bank is {tuple(self.sky_bank.shape[1:])}, the cropped ISR {(ch, cw)}')
+        self.isr_noise = bool(isr_noise)
+        self.isr_noise_seed, self._isr_noise_calls = torch.initial_seed() & (2 ** 63 - 1), 0
 
     def raw(self, idx):
         """(frame uint8 [H,W,3], previous frame uint8 [H,W,3], label int64 [rh,rw] at the resized resolution)"""
@@ -158,11 +170,14 @@ class CityscapesICDataset(_SyntheticBase):
         if 'image' in self.outputs or need_isr:
             r = pl.pil_resize_u8(now, samp, (W, H), (rw, rh), (cw, ch), norm=(pl.IMAGENET_MEAN, pl.IMAGENET_STD), want_gray=need_isr)
             out['image'] = r['f']
-        if 'label' in self.outputs:
+        augment = need_isr and (self.sky_bank is not None or self.isr_noise)
+        labs = None
+        if 'label' in self.outputs or (need_isr and self.sky_bank is not None):
             labs = []
             for (_, _, lab), x, y, f in zip(raws, xs, ys, flips):
                 lab = lab[y:y + ch, x:x + cw]
                 labs.append((torch.flip(lab, dims=[-1]) if f else lab)[None])
+        if 'label' in self.outputs:
             # the class set ClassMix draws from (dacs_transforms.py:103-104: unique over the whole batch), taken HERE on the host
             # from the cropped labels: the training step then needs no device read at all for it (the reference's
             # `torch.unique(labels)` + `.cpu()` is a sync; a side-stream read would have to be ordered after the copy below)
@@ -170,6 +185,8 @@ class CityscapesICDataset(_SyntheticBase):
             classes = torch.unique(torch.stack(labs))
             out['label'] = _stack_dev(labs, dev)
             out['label']._cmda_classes = classes
+            # per-sample sky pixel counts: where DACS' sky mask stops drawing (ops.draw_sky_mask), same staleness key
+            out['label']._cmda_sky_counts = [int((lab == 10).sum()) for lab in labs]
             # (validated by the consumer: an in-place refill of this buffer bumps _version and the stale set is dropped)
             out['label']._cmda_classes_key = (out['label'].data_ptr(), out['label']._version)
             if dev.type == 'cuda':
@@ -188,6 +205,24 @@ class CityscapesICDataset(_SyntheticBase):
                 isr.append(ops.isr_from_gray(r['gray'][b:b + 1], self.isr_parms['val_range'], self.isr_parms['_threshold'],
                                              self.isr_parms['_clip_range'], self.isr_parms['shift_pixel'], d))
             out['img_self_res'] = torch.cat(isr)
+        if augment:
+            # cityscapes_ic.py:241-261 per sample: sky_mask_transform's draws, then the noise's
+            sky, noise = [], []
+            for b in range(B):
+                if self.sky_bank is not None:
+                    sky.append(ops.draw_sky_mask(self.sky_bank.shape[0], ch, cw, int((labs[b] == 10).sum())))
+                if self.isr_noise:
+                    noise.append(ops.draw_isr_noise('noise+blur', source='random'))
+            x = out['img_self_res']
+            if sky:
+                lab_dev = out['label'] if 'label' in out else _stack_dev(labs, dev)
+                prm, rows, cols = (t.to(dev) for t in ops.sky_mask_params(sky))
+                x = ops.sky_mask(lab_dev, x, self.sky_bank, prm, rows, cols, k_host=[d['k'] for d in sky])
+            if noise:
+                x = ops.isr_noise(x, ops.isr_noise_params(noise).to(dev), 'noise+blur', seed=self.isr_noise_seed,
+                                  offset=self._isr_noise_calls)
+                self._isr_noise_calls += 1
+            out['img_self_res'], self.last_isr_draws = x, dict(sky=sky or None, isr_noise=noise or None)
         return out
 
     def sample_class_stats(self, n=256):

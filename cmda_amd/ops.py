@@ -1119,3 +1119,169 @@ def gaussian_blur_(img, taps_x, taps_y, enable=None):
     call('cmda_gaussian_blur', ptr(img), ptr(tmp), ptr(taps_x), ptr(taps_y), c_i32(B * C), c_i32(H), c_i32(W),
          c_i32(taps_x.numel()), c_i32(taps_y.numel()), ptr(enable), stream_of(img))
     return img
+
+
+# ---- ISR augmentations (isr_augment.hip, include/cmda_hip_ext3.h): sky mask and sensor noise ----------------------------------------
+SKY_CHUNK = 8          # chunk size of the noise shuffle (dacs_transforms.py:138)
+SKY_MIN_PIXELS = 10    # fewer sky pixels: sky_mask_transform returns its input (:140)
+ISR_NOISE_TYPES = ('', 'noise', 'blur', 'noise+blur')
+# ranges of add_noise_on_isr's draws (dacs_transforms.py:196-198; cityscapes_ic.py:85-87): |n1| < t1 keeps, |n2| < t2 adds, intensity
+ISR_NOISE_RANGES = ((1.0, 1.5), (0.4, 0.6), (0.1, 0.3))
+
+
+def load_noise_bank(src):
+    """the sky-mask noise bank as a CPU uint8 tensor [N,H,W].  `src`: a directory, read as the reference reads it (os.listdir order,
+    one image per file through PIL; `.npy` files are accepted as well), or a uint8 tensor / array [N,H,W]."""
+    if isinstance(src, (str, os.PathLike)):
+        imgs = []
+        for name in os.listdir(src):
+            path = os.path.join(src, name)
+            if name.endswith('.npy'):
+                a = np.load(path)
+            else:
+                from PIL import Image
+                a = np.array(Image.open(path))
+            imgs.append(torch.from_numpy(np.ascontiguousarray(a)))
+        if not imgs:
+            raise ValueError(f'sky_mask: no noise image in {src!r}')
+        bank = torch.stack(imgs)
+    else:
+        bank = torch.as_tensor(src)
+    if bank.dtype != torch.uint8 or bank.dim() != 3 or bank.shape[0] < 1:
+        raise ValueError(f'sky_mask: the noise bank must be uint8 [N,H,W], got {bank.dtype} {tuple(bank.shape)}')
+    return bank.contiguous()
+
+
+def _shuffled_axis(n):
+    """torch.split(chunk 8) -> randperm over the chunks -> cat (dacs_transforms.py:162-166) as the source index of every output
+    index; a short last chunk moves like any other"""
+    chunks = torch.split(torch.arange(n, dtype=torch.int32), SKY_CHUNK)
+    order = torch.randperm(len(chunks))
+    return torch.cat([chunks[int(i)] for i in order])
+
+
+def draw_sky_mask(n_noise, H, W, sky_count=None):
+    """The host decisions of ONE sky_mask_transform call, drawn from the torch CPU generator in the reference's order:
+    randint(21, 61) (made odd), uniform_(0.1, 0.3), uniform_(0.5, 1.2), randint(0, n_noise), randperm(row chunks), randperm(column
+    chunks).  With `sky_count` given and below 10 it stops after the third draw, as the reference's early return does.  Without
+    `sky_count` all six are drawn always -- the kernel decides on the device whether the sample is transformed -- so the torch
+    stream then differs from the reference's for samples with fewer than 10 sky pixels.
+    Returns dict(k, lam, intensity, index, rows int32 [H], cols int32 [W]): rows / cols = the bank row / column per output row / column."""
+    k = int(torch.randint(21, 61, size=(1,)).item())
+    lam = torch.empty(size=(1,)).uniform_(0.1, 0.3).item()
+    intensity = torch.empty(size=(1,)).uniform_(0.5, 1.2).item()
+    if k % 2 == 0:
+        k += 1
+    d = dict(k=k, lam=lam, intensity=intensity, index=0, rows=None, cols=None)
+    if sky_count is not None and int(sky_count) < SKY_MIN_PIXELS:
+        d['rows'], d['cols'] = torch.arange(H, dtype=torch.int32), torch.arange(W, dtype=torch.int32)
+        return d
+    d['index'] = int(torch.randint(0, n_noise, size=(1,)).item())
+    d['rows'] = _shuffled_axis(H)
+    d['cols'] = _shuffled_axis(W)
+    return d
+
+
+def _f32_bits(values):
+    return torch.tensor(values, dtype=torch.float32).view(torch.int32)
+
+
+def sky_mask_params(draws):
+    """list of draw_sky_mask dicts -> CPU (prm int32 [B,4], rows int32 [B,H], cols int32 [B,W]): the layout cmdax3_sky_mask reads"""
+    prm = torch.empty(len(draws), 4, dtype=torch.int32)
+    prm[:, 0] = torch.tensor([d['k'] for d in draws], dtype=torch.int32)
+    prm[:, 1] = torch.tensor([d['index'] for d in draws], dtype=torch.int32)
+    prm[:, 2] = _f32_bits([d['lam'] for d in draws])
+    prm[:, 3] = _f32_bits([d['intensity'] for d in draws])
+    return prm, torch.stack([d['rows'] for d in draws]), torch.stack([d['cols'] for d in draws])
+
+
+def sky_mask(label, isr, bank, prm, rows, cols, enable=None, out=None, debug=False, k_host=None):
+    """sky_mask_transform for a batch (three launches, no host sync).  label uint8 / int64 [B,H,W] (or [B,1,H,W]); isr fp32
+    [B,C,H,W], C in {1, 3}; bank uint8 [N,H,W]; prm / rows / cols: DEVICE tensors in the layout of `sky_mask_params`; enable:
+    optional DEVICE int32 [B].  A sample with fewer than 10 sky pixels, a closed gate or an invalid k comes back bit-equal to its
+    input.  An all-sky sample, where the reference divides 0 by 0, takes a normalised weight of 0 (blur_w = 1) and stays finite.
+    Out of place unless `out` is given (`out=isr` is allowed).  debug: also return (expansion, blur_w) fp32 [B,H,W].
+    k_host: the kernel sizes as the host knows them, checked before anything is launched."""
+    check_dev(label, isr, bank, prm, rows, cols, enable, out)
+    B, C, H, W = isr.shape
+    if isr.dtype != torch.float32 or bank.dtype != torch.uint8 or bank.dim() != 3:
+        raise L.CmdaError('sky_mask: isr must be fp32 and the bank uint8 [N,H,W]')
+    if label.numel() != B * H * W:
+        raise L.CmdaError(f'sky_mask: label {tuple(label.shape)} does not match isr {tuple(isr.shape)}')
+    assert prm.shape == (B, 4) and prm.dtype == torch.int32 and rows.shape == (B, H) and cols.shape == (B, W)
+    assert rows.dtype == torch.int32 and cols.dtype == torch.int32 and (enable is None or enable.dtype == torch.int32)
+    if out is None:
+        out = torch.empty_like(isr)
+    dbg_e = torch.empty(B, H, W, dtype=torch.float32, device=isr.device) if debug else None
+    dbg_w = torch.empty(B, H, W, dtype=torch.float32, device=isr.device) if debug else None
+    ws = torch.empty(max(1, L.lib().cmdax3_sky_mask_ws_bytes(B, H, W)), dtype=torch.uint8, device=isr.device)
+    kc = (ctypes.c_int * B)(*[int(v) for v in k_host]) if k_host is not None else None
+    call('cmdax3_sky_mask', ptr(label), c_i32(L.label_tag(label)), ptr(isr), ptr(bank), ptr(prm), ptr(rows), ptr(cols), ptr(enable),
+         ptr(out), ptr(dbg_e), ptr(dbg_w), ptr(ws), kc, c_i32(B), c_i32(C), c_i32(H), c_i32(W), c_i32(bank.shape[0]),
+         c_i32(bank.shape[1]), c_i32(bank.shape[2]), stream_of(isr))
+    return (out, dbg_e, dbg_w) if debug else out
+
+
+def draw_isr_noise(mode, source='torch'):
+    """The host decisions of ONE add_noise_on_isr call -> (blur gate, t1, t2, intensity).  source 'torch' (DACS,
+    dacs_transforms.py:186-211): torch.rand(1) coin when `mode` has 'blur', then three uniform_ draws when it has 'noise'.
+    source 'random' (the loader, cityscapes_ic.py:244-257): the same coin, then random.uniform x 3.  The reference's randn_like
+    fields are NOT drawn here: the kernel generates its own (`isr_noise`), which consumes nothing from torch's generators."""
+    import random
+    blur, t = 0, [0.0, 0.0, 0.0]
+    if 'blur' in mode:
+        blur = int(bool(torch.rand(1) < 0.5))
+    if 'noise' in mode:
+        for i, rng in enumerate(ISR_NOISE_RANGES):
+            t[i] = random.uniform(*rng) if source == 'random' else torch.empty(size=(1,)).uniform_(*rng).item()
+    return (blur, t[0], t[1], t[2])
+
+
+def isr_noise_params(draws):
+    """list of draw_isr_noise tuples -> CPU int32 [B,4]: the layout cmdax3_isr_noise reads"""
+    prm = torch.empty(len(draws), 4, dtype=torch.int32)
+    prm[:, 0] = torch.tensor([d[0] for d in draws], dtype=torch.int32)
+    for j in (1, 2, 3):
+        prm[:, j] = _f32_bits([d[j] for d in draws])
+    return prm
+
+
+def _offset_args(offset, offset_dev):
+    if offset_dev is not None:
+        assert offset_dev.dtype == torch.int64 and offset_dev.numel() == 1
+    return c_i64(int(offset)), ptr(offset_dev)
+
+
+def randn_fields(B, H, W, seed, offset=0, offset_dev=None, device=None):
+    """fp32 [3,B,H,W]: the three standard-normal fields `isr_noise` generates for (seed, offset [+ the DEVICE int64 offset_dev])
+    -- Philox4x32-10 + Box-Muller, counter (offset, sample, field, pixel); no generator of torch is touched"""
+    check_dev(offset_dev)
+    dev = offset_dev.device if offset_dev is not None else torch.device(device if device is not None else ('cpu' if L.emulated() else 'cuda'))
+    out = torch.empty(3, B, H, W, dtype=torch.float32, device=dev)
+    off, offd = _offset_args(offset, offset_dev)
+    call('cmdax3_randn_fields', ptr(out), c_i32(B), c_i32(H), c_i32(W), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), off, offd,
+         stream_of(out))
+    return out
+
+
+def isr_noise(isr, prm, mode, fields=None, seed=0, offset=0, offset_dev=None, enable=None, out=None):
+    """add_noise_on_isr on channel 0 of the fp32 NCHW [B,C,H,W] ISR, the result on all C channels (one launch).  prm: DEVICE int32
+    [B,4] (`isr_noise_params`); mode in ISR_NOISE_TYPES; fields: optional fp32 [3,B,H,W] (n1, n2, n3) -- without them the kernel
+    generates `randn_fields(seed, offset)` in registers, bit-equal to passing those; enable: optional DEVICE int32 [B]."""
+    check_dev(isr, prm, fields, offset_dev, enable, out)
+    if mode not in ISR_NOISE_TYPES:
+        raise ValueError(f'isr_noise: mode {mode!r} not in {ISR_NOISE_TYPES}')
+    B, C, H, W = isr.shape
+    assert isr.dtype == torch.float32 and prm.shape == (B, 4) and prm.dtype == torch.int32
+    assert enable is None or enable.dtype == torch.int32
+    if fields is not None:
+        assert fields.shape == (3, B, H, W) and fields.dtype == torch.float32
+    if out is None:
+        out = torch.empty_like(isr)
+    n = [None] * 3 if fields is None else [fields[0], fields[1], fields[2]]
+    off, offd = _offset_args(offset, offset_dev)
+    call('cmdax3_isr_noise', ptr(isr), ptr(out), ptr(n[0]), ptr(n[1]), ptr(n[2]), ptr(prm), ptr(enable), c_i32(B), c_i32(C), c_i32(H),
+         c_i32(W), c_i32(int('blur' in mode)), c_i32(int('noise' in mode)), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), off, offd,
+         stream_of(isr))
+    return out

@@ -18,7 +18,11 @@ The image-only train types 'cs2dsec_image' / 'cs2dz_image' (DAFormer's DACS on o
 fusion types are compared against; dacs.py:363-377 and the image branches below) run through `_iteration_image`: no events, no ISR,
 no fusion; for 'cs2dz_image' optionally the frozen 3 -> 3 day -> night generator on the source image (cyclegan_id2in_path).
 Out of scope here: the remaining train types ('cs2dz_image+d2n-isr', '_split', '_no-fusion'), OrgDACS,
-LightNet (cyclegan_light_path), the matplotlib debug panels, sky-mask / flare / cow-mask augmentations.
+LightNet (cyclegan_light_path), the matplotlib debug panels, flare / cow-mask / deflare augmentations.
+ISR augmentations (isr_augment.hip): `sky_mask` (dacs.py:431-434, the source ISR before the student sees it) and `isr_noise_dacs_type`
+(dacs.py:753-755, on the ISR recomputed from the mixed image) run as batched launches whose per-sample draws travel in the control
+block; the noise fields come from a counter-based generator in the kernel (seed fixed at construction, offset = the iteration counter),
+not from torch's generators.
 """
 import contextlib
 import os
@@ -143,7 +147,17 @@ class DACS(nn.Module):
                                                             pretrained=m.get('pretrained'), train_cfg=m.get('train_cfg'),
                                                             test_cfg=m.get('test_cfg'))))
         self.debug_fdist_mask = self.debug_gt_rescale = None
-        assert cfg.get('sky_mask') is None, 'sky-mask augmentation is off in configs/fusion/* and not implemented'
+        # ISR augmentations of the night-robustness recipe (dacs.py:125-129, :153-157): the noise bank lives on the device from here on
+        bank = None
+        if cfg.get('sky_mask') is not None:
+            assert not self.image_only, 'sky_mask acts on the source ISR: the image-only train types have none'
+            bank = ops.load_noise_bank(cfg['sky_mask'])
+        self.register_buffer('sky_bank', bank, persistent=False)   # (a buffer: it moves with the module; not part of the state dict)
+        self.isr_noise_dacs_type = cfg.get('isr_noise_dacs_type') or ''
+        assert self.isr_noise_dacs_type in ops.ISR_NOISE_TYPES, f'isr_noise_dacs_type {self.isr_noise_dacs_type!r} not in {ops.ISR_NOISE_TYPES}'
+        assert not (self.isr_noise_dacs_type and self.image_only), 'isr_noise_dacs_type acts on the mixed ISR: the image-only train types have none'
+        # key of the kernel's noise generator; the per-iteration offset is the iteration counter, staged in the control block
+        self.isr_noise_seed = torch.initial_seed() & (2 ** 63 - 1)
         self.mixed_image_to_mixed_isr = bool(cfg.get('mixed_image_to_mixed_isr'))
         self.isr_parms = {'val_range': (1, 10 ** 2), '_threshold': 0.04, '_clip_range': 0.2, 'shift_pixel': 3}
         if cfg.get('isr_parms'):
@@ -340,6 +354,12 @@ class DACS(nn.Module):
             d['choice'] = 2.0
         else:
             d['choice'] = float(torch.rand(1))   # CPU generator: no device sync
+        d['sky'] = d['isr_noise'] = None
+        if self.sky_bank is not None:
+            # dacs.py:431-434: one sky_mask_transform per sample, right behind the events / ISR choice.  With the loader's per-sample
+            # sky counts the draws stop where the reference's early return stops them; without, all six are drawn (ops.draw_sky_mask)
+            counts = self._sky_counts(day_label)
+            d['sky'] = [ops.draw_sky_mask(self.sky_bank.shape[0], H, W, None if counts is None else counts[b]) for b in range(B)]
         d['color_jitter'] = random.uniform(0, 1)
         d['blur'] = random.uniform(0, 1) if self.blur else 0
         d['sigma'] = random.uniform(0.15, 1.15)
@@ -355,7 +375,17 @@ class DACS(nn.Module):
             d['direction'] = _DIRECT[int(cj * 10) % 2][int(cj * 100) % 2]
         else:
             d['direction'] = self.shift_type
+        if self.isr_noise_dacs_type:   # dacs.py:753-755: add_noise_on_isr's host draws, per sample, last in the mixing loop
+            d['isr_noise'] = [ops.draw_isr_noise(self.isr_noise_dacs_type) for _ in range(B)]
         return d
+
+    @staticmethod
+    def _sky_counts(labels):
+        """per-sample sky pixel counts the loader attached to the label tensor (datasets.CityscapesICDataset), None when absent or stale"""
+        counts = getattr(labels, '_cmda_sky_counts', None)
+        if counts is not None and getattr(labels, '_cmda_classes_key', None) != (labels.data_ptr(), labels._version):
+            counts = None
+        return counts
 
     # -- device-resident control block: what the host decided, in buffers whose addresses never change ----------------------
     def _control_block(self, dev, B, H, W):
@@ -367,6 +397,10 @@ class DACS(nn.Module):
         ndir = 4 if self.shift_type == 'all' else 2
         al = lambda n: (n + 3) // 4 * 4  # noqa: E731  (16-byte aligned sections)
         sizes = [('classes', 2 * B * self._kmax()), ('jitter', 8 * B), ('taps_x', kx), ('taps_y', ky), ('dirs', 2 * ndir), ('flags', 4)]
+        if self.sky_bank is not None:
+            sizes += [('sky_prm', 4 * B), ('sky_rows', B * H), ('sky_cols', B * W)]
+        if self.isr_noise_dacs_type:
+            sizes += [('noise_prm', 4 * B), ('offset', 2)]
         off, o = {}, 0
         for name, n in sizes:
             off[name] = (o, n)
@@ -380,9 +414,14 @@ class DACS(nn.Module):
 
         def views(buf):
             v = {n: buf[a:a + ln] for n, (a, ln) in off.items()}
-            return dict(classes=v['classes'].view(torch.int64).view(B, self._kmax()), jitter=v['jitter'].view(torch.float32).view(B, 8),
-                        taps_x=v['taps_x'].view(torch.float32), taps_y=v['taps_y'].view(torch.float32),
-                        dirs=v['dirs'].view(ndir, 2), jitter_on=v['flags'][0:1], blur_on=v['flags'][1:2])
+            d = dict(classes=v['classes'].view(torch.int64).view(B, self._kmax()), jitter=v['jitter'].view(torch.float32).view(B, 8),
+                     taps_x=v['taps_x'].view(torch.float32), taps_y=v['taps_y'].view(torch.float32),
+                     dirs=v['dirs'].view(ndir, 2), jitter_on=v['flags'][0:1], blur_on=v['flags'][1:2])
+            if 'sky_prm' in v:
+                d.update(sky_prm=v['sky_prm'].view(B, 4), sky_rows=v['sky_rows'].view(B, H), sky_cols=v['sky_cols'].view(B, W))
+            if 'noise_prm' in v:
+                d.update(noise_prm=v['noise_prm'].view(B, 4), offset=v['offset'].view(torch.int64))
+            return d
         self._ctl = dict(key=key, hosts=hosts, hviews=[views(h) for h in hosts], events=[None] * nring, slot=0, dev=devbuf,
                          d=views(devbuf), kx=kx, ky=ky)
         return self._ctl
@@ -405,6 +444,12 @@ class DACS(nn.Module):
             h['taps_x'].copy_(ops.gaussian_taps(cb['kx'], draws['sigma']))
             h['taps_y'].copy_(ops.gaussian_taps(cb['ky'], draws['sigma']))
         h['dirs'].copy_(torch.tensor(ops.isr_dirs(draws['direction'], self.isr_parms['shift_pixel']), dtype=torch.int32))
+        if 'sky_prm' in h:
+            prm, rows, cols = ops.sky_mask_params(draws['sky'])
+            h['sky_prm'].copy_(prm), h['sky_rows'].copy_(rows), h['sky_cols'].copy_(cols)
+        if 'noise_prm' in h:
+            h['noise_prm'].copy_(ops.isr_noise_params(draws['isr_noise']))
+            h['offset'][0] = self.local_iter
         cb['dev'].copy_(cb['hosts'][slot], non_blocking=True)
         if cb['dev'].is_cuda:
             ev = cb['events'][slot] or torch.cuda.Event()
@@ -555,6 +600,9 @@ class DACS(nn.Module):
         one = rt.ones1(dev)
         lab = day_label.view(B, H, W)
         classes = ctl['classes']
+        if self.sky_bank is not None:
+            # dacs.py:431-434, before anything reads the source ISR; out of place: the loader's buffers are reused
+            day_isr = ops.sky_mask(lab, day_isr, self.sky_bank, ctl['sky_prm'], ctl['sky_rows'], ctl['sky_cols'])
         # Schedule.  The reference runs source step, teacher, mixing, mixed step one after the other (dacs.py:489-860), but the
         # only data dependencies are: mixing needs the teacher's pseudo-labels and the generator's events; the student's
         # gradients are the sum over both steps; its BatchNorm running statistics see the source step before the mixed step.
@@ -578,6 +626,9 @@ class DACS(nn.Module):
             gray = ops.isr_gray(mixed_img)
             mixed_isr = ops.isr_from_gray(gray, self.isr_parms['val_range'], self.isr_parms['_threshold'],
                                           self.isr_parms['_clip_range'], self.isr_parms['shift_pixel'], direction, dirs_dev=ctl['dirs'])
+            if self.isr_noise_dacs_type:   # dacs.py:753-755: channel 0 through add_noise_on_isr, the result on all three channels
+                mixed_isr = ops.isr_noise(mixed_isr, ctl['noise_prm'], self.isr_noise_dacs_type, seed=self.isr_noise_seed,
+                                          offset_dev=ctl['offset'])
             return mixed_img, mixed_isr
 
         # EARLY-STUDENT schedule (lane 'T' enabled): the student's forward pass needs the MIXED INPUTS, which depend on the source labels,
@@ -678,6 +729,8 @@ class DACS(nn.Module):
         extras = dict(mixed_img=mixed_img, mixed_lbl=mixed_lbl, mixed_isr=mixed_isr, pseudo_weight=mixed_weight,
                       pseudo_label=pseudo_label, classes=classes, mixed_events=mixed_events, day_events=day_events,
                       teacher_logits=ema, pseudo_count=count)
+        if self.sky_bank is not None:
+            extras['day_isr'] = day_isr   # the sky-masked source ISR the student saw
         return log_vars, self._with_fdist(extras, fd)
 
     def _iteration_image(self, src, tgt, ctl):
@@ -778,6 +831,8 @@ class DACS(nn.Module):
         day_label = src['label']
         B, _, H, W = src['image'].shape
         dev = src['image'].device
+        if self.sky_bank is not None and tuple(self.sky_bank.shape[1:]) != (H, W):
+            raise ValueError(f'sky_mask: the noise bank is {tuple(self.sky_bank.shape[1:])}, the source ISR {(H, W)}')
         draws = self.inject_draws or self._draw(day_label, H, W)
         self.last_draws = draws
         if not self.image_only:
