@@ -1,5 +1,5 @@
 """ctypes binding of libcmda_hip.so (the C ABI declared in include/cmda_hip.h and its extensions include/cmda_hip_ext.h,
-include/cmda_hip_ext2.h and include/cmda_hip_ext3.h).
+include/cmda_hip_ext2.h, include/cmda_hip_ext3.h and include/cmda_hip_ext4.h).
 
 The product path has exactly one backend: the gfx950 kernel library built in-tree by
 ``__graft_entry__.build()`` / ``make hip``.  If it is missing, or a tensor is not on the GPU,
@@ -23,6 +23,7 @@ U8, I64 = 0, 1   # integer label tensors of the extension entry points (CMDAX_U8
 ABI_VERSION, ABI_EXT_VERSION = 8, 1
 ABI_EXT2_VERSION = 1
 ABI_EXT3_VERSION = 1
+ABI_EXT4_VERSION = 1
 
 
 class View(ctypes.Structure):
@@ -82,6 +83,14 @@ def _declare(lib):
         raise CmdaError('libcmda_hip.so third ABI table (cmdax3_*) version mismatch')
     lib.cmdax3_sky_mask_ws_bytes.restype = ctypes.c_int64
     lib.cmdax3_sky_mask_ws_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    # the fourth table (include/cmda_hip_ext4.h): multi-parameter ISR and cow mask
+    if not hasattr(lib, 'cmdax4_abi_version'):
+        raise CmdaError('the kernel library lacks the fourth ABI table (cmdax4_*): rebuild it')
+    lib.cmdax4_abi_version.restype = ctypes.c_int
+    if lib.cmdax4_abi_version() != ABI_EXT4_VERSION:
+        raise CmdaError('libcmda_hip.so fourth ABI table (cmdax4_*) version mismatch')
+    lib.cmdax4_cow_mask_ws_bytes.restype = ctypes.c_int64
+    lib.cmdax4_cow_mask_ws_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     return lib
 
 

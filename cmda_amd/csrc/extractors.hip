@@ -10,15 +10,9 @@
 // (2) Event voxel grid: mmseg/datasets/dsec.py events_to_voxel_grid :26-70 (tri-linear scatter-add of polarity) and
 //     events_norm :80-121 (non-zero standardise, clip, +/- min-max).
 // All HBM/atomic-bound; fp32 throughout; min/max via integer atomics on the (non-negative) float bit patterns.
-#include "common.h"
+#include "isr_common.h"   // minmax_init_kernel, isr_diff, isr_norm (shared with isr_multi.hip)
 
 namespace {
-
-// min/max scratch: per record {min=+inf, max=0, min=+inf, max=0} as float bit patterns (non-negative floats order like uints)
-__global__ void minmax_init_kernel(unsigned* __restrict__ mm, int nrec) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nrec * 4) mm[i] = (i & 1) ? 0u : 0x7F800000u;
-}
 
 // ---------------------------------------------------------------------------------------------------- ISR
 // img: NCHW fp32 [B,3,H,W] (normalised), gray: uint8 [B,H,W]
@@ -42,17 +36,6 @@ __global__ void isr_gray_kernel(const float* __restrict__ img, unsigned char* __
     }
     gray[i] = (unsigned char)((19595u * u[0] + 38470u * u[1] + 7471u * u[2] + 0x8000u) >> 16);
   }
-}
-
-static __device__ __forceinline__ float isr_diff(const unsigned char* __restrict__ g, const float* __restrict__ lut,
-                                                 int y, int x, int H, int W, int dy, int dx, float thr) {
-  // shifted copy with "edge = itself" semantics of np.concatenate in get_image_change_from_pil
-  const int sy = y + dy, sx = x + dx;
-  const bool inside = sy >= 0 && sy < H && sx >= 0 && sx < W;
-  const float front = lut[g[y * W + x]];
-  const float now = inside ? lut[g[sy * W + sx]] : front;
-  const float d = now - front;
-  return fabsf(d) <= thr ? 0.f : d;
 }
 
 // mm[b][dir][4] (as uint bit patterns of non-negative floats): pos_min, pos_max, negabs_min, negabs_max
@@ -104,17 +87,8 @@ __global__ void isr_apply_kernel(const unsigned char* __restrict__ gray, const f
     const unsigned char* g = gray + (long)b * H * W;
     float acc = 0.f;
     for (int dir = 0; dir < ndir; ++dir) {
-      const unsigned* m = mm + ((long)b * ndir + dir) * 4;
-      const float pmin = __uint_as_float(m[0]), pmax = __uint_as_float(m[1]);
-      const float namin = __uint_as_float(m[2]), namax = __uint_as_float(m[3]);
       const float d = isr_diff(g, lut, y, x, H, W, dirs[dir * 2], dirs[dir * 2 + 1], thr);
-      const float pos = fminf(fmaxf(d, 0.f), clip);
-      const float neg = fminf(fmaxf(d, -clip), 0.f);
-      // tensor_normalize_to_range: (t - tmin) / (tmax - tmin + 1e-8) * (hi - lo) + lo
-      const float pn = (pos - pmin) / (pmax - pmin + 1e-8f) * 1.f + 0.f;
-      const float nlo = -namax, nhi = -namin;  // min / max of the negative part
-      const float nn = (neg - nlo) / (nhi - nlo + 1e-8f) * 1.f + -1.f;
-      acc += (pn + nn) * share;
+      acc += isr_norm(d, clip, mm + ((long)b * ndir + dir) * 4) * share;
     }
     float* o = out + (long)b * 3 * H * W + p;
     o[0] = acc; o[(long)H * W] = acc; o[2L * H * W] = acc;

@@ -29,6 +29,30 @@ PALETTE = [[128, 64, 128], [244, 35, 232], [70, 70, 70], [102, 102, 156], [190, 
            [0, 60, 100], [0, 80, 100], [0, 0, 230], [119, 11, 32]]
 _DIRECT = [['leftdown', 'leftup'], ['rightdown', 'rightup']]
 _DEFAULT_ISR = {'val_range': (1, 10 ** 2), '_threshold': 0.04, '_clip_range': 0.2, 'shift_pixel': 3}   # dsec.py:180, cityscapes_ic.py
+COW_MASK_PAD = 97   # (K - 1) / 2 of cow_masks' 195-tap blur (utils.py:165, max_sigma 16): the reflect padding needs a longer side
+
+
+def _isr3(val_range, rows):
+    return [dict(val_range=val_range, _threshold=t, _clip_range=c, shift_pixel=s) for t, c, s in rows]
+
+
+# The reference's three-channel ISR parameter sets (`shift_3_channel`): shift 1 / 3 / 5 pixels, each with its own dead zone and clip
+# range, one value range per set.
+ISR3_PRESETS = {
+    'day': _isr3((1, 10), [(0.025, 0.05, 1), (0.030, 0.20, 3), (0.040, 0.32, 5)]),                      # cityscapes_ic.py:101-105
+    'new_day': _isr3((1e-5, 255 + 1e-5), [(0, 0.015, 1), (0, 0.040, 3), (0, 0.070, 5)]),               # cityscapes_ic.py:106-110
+    'night': _isr3((9, 255 + 9), [(0.012, 0.04, 1), (0.012, 0.12, 3), (0.012, 0.20, 5)]),             # dark_zurich_ic.py:112-116
+    'new_night': _isr3((500, 1000), [(0.015, 0.05, 1), (0.02, 0.12, 3), (0.025, 0.2, 5)]),            # dark_zurich_ic.py:117-121
+    'dacs': _isr3((9, 255 + 9), [(0.012, 0.04, 1), (0.012, 0.12, 3), (0.012, 0.20, 5)]),              # dacs.py:162-165
+}
+
+
+def check_isr3(parms):
+    """list-form `isr_parms`: three dicts (val_range, _threshold, _clip_range, shift_pixel) under ONE value range -> a list of copies"""
+    parms = [dict(p) for p in parms]
+    assert len(parms) == 3, f'a three-channel isr_parms holds three dicts, got {len(parms)}'
+    assert len({tuple(float(v) for v in p['val_range']) for p in parms}) == 1, 'the three isr_parms rows share one val_range'
+    return parms
 
 
 def _device(device):
@@ -98,7 +122,14 @@ class CityscapesICDataset(_SyntheticBase):
     of the crop's size) and `isr_noise=True` apply the two ISR augmentations of cityscapes_ic.py:241-261, :303-336 to 'img_self_res' on
     the device (ops.sky_mask, ops.isr_noise), per sample in the reference's order: sky-mask draws (torch generator), then the blur coin
     (torch) and random.uniform x 3.  The noise fields come from the kernel's counter-based generator (seed = torch.initial_seed() at
-    construction, offset = the number of batches made so far), not from torch.randn_like."""
+    construction, offset = the number of batches made so far), not from torch.randn_like.
+    `isr_parms` given as a LIST of three dicts under one value range (e.g. `ISR3_PRESETS['new_day']`) selects the three-channel ISR of
+    cityscapes_ic.py:224-230 -- one `ops.isr_multi` call per batch, direction 'rightdown' whatever `shift_type` says, as there; the
+    reference's own spelling `shift_3_channel=True` stays refused on this dataset.  With it `isr_noise` draws independent fields
+    per channel (the reference's randn_like on [3,H,W]).  `isr_cow_mask=True` (cityscapes_ic.py:263-266) multiplies the ISR by a cow
+    mask after the noise (`ops.cow_mask`, one call per batch): per sample torch.randn([1]).uniform_ twice, after that sample's sky-mask
+    and noise draws; the noise field is the kernel's (seed as above, offset = the number of cow-mask batches so far).  It needs a
+    crop of at least 98 x 98 (reflect padding of 97), as the reference does."""
 
     def __init__(self, dataset_path='', image_resize_size=(1024, 512), image_crop_size=(512, 512), image_change_range=1,
                  classes=CLASSES, palette=PALETTE, return_GI_or_IC='image_change', isr_shift_pixel=4, enforce_3_channels=True,
@@ -107,14 +138,20 @@ class CityscapesICDataset(_SyntheticBase):
                  synthetic_length=2975, raw_size=(2048, 1024), seed=0, device=None):
         _warn_synthetic(type(self), dataset_path)
         assert image_crop_size[0] <= image_resize_size[0] and image_crop_size[1] <= image_resize_size[1]
-        assert not (isr_cow_mask or high_resolution_isr or shift_3_channel) and random_flare is None, \
-            'isr_cow_mask, high_resolution_isr, shift_3_channel and random_flare are not implemented'
+        assert not high_resolution_isr and random_flare is None, 'high_resolution_isr and random_flare are not implemented'
+        assert not shift_3_channel, \
+            "shift_3_channel is not accepted here: pass the three parameter rows, e.g. isr_parms=datasets.ISR3_PRESETS['new_day']"
+        assert not isr_cow_mask or min(image_crop_size) > COW_MASK_PAD, \
+            f'isr_cow_mask reflect-pads the crop by {COW_MASK_PAD} pixels: both sides of image_crop_size must be at least {COW_MASK_PAD + 1}'
         assert shift_type in {'all', 'random', 'rightdown'}
         self.image_resize_size, self.image_crop_size = tuple(image_resize_size), tuple(image_crop_size)
         self.outputs, self.CLASSES, self.PALETTE = set(outputs), classes, palette
-        self.isr_parms = dict(isr_parms) if isr_parms != '' else dict(_DEFAULT_ISR, shift_pixel=isr_shift_pixel)
+        self.isr3 = check_isr3(isr_parms) if isinstance(isr_parms, (list, tuple)) else None
+        self._isr3_prm = None
+        self.isr_parms = dict(_DEFAULT_ISR, shift_pixel=isr_shift_pixel) if (isr_parms == '' or self.isr3) else dict(isr_parms)
         self.shift_type, self.enforce_3_channels = shift_type, enforce_3_channels
         self.length, self.raw_size, self.seed, self.device = synthetic_length, tuple(raw_size), seed, _device(device)
+        self.isr_cow_mask, self._cow_calls = bool(isr_cow_mask), 0
         self.file_path = {'label': [f'synthetic/{i:06d}_gtFine_labelTrainIds.png' for i in range(min(synthetic_length, 4096))]}
         self.sky_bank = None
         if sky_mask is not None:
@@ -170,7 +207,7 @@ class CityscapesICDataset(_SyntheticBase):
         if 'image' in self.outputs or need_isr:
             r = pl.pil_resize_u8(now, samp, (W, H), (rw, rh), (cw, ch), norm=(pl.IMAGENET_MEAN, pl.IMAGENET_STD), want_gray=need_isr)
             out['image'] = r['f']
-        augment = need_isr and (self.sky_bank is not None or self.isr_noise)
+        augment = need_isr and (self.sky_bank is not None or self.isr_noise or self.isr_cow_mask)
         labs = None
         if 'label' in self.outputs or (need_isr and self.sky_bank is not None):
             labs = []
@@ -198,7 +235,11 @@ class CityscapesICDataset(_SyntheticBase):
             t = pl.pil_resize_u8(tr.view(B, H, W, 1), samp, (W, H), (rw, rh), (cw, ch), norm=((0.5,) * 3, (0.5,) * 3),
                                  rep3=self.enforce_3_channels)
             out['img_time_res'] = t['f']
-        if need_isr:
+        if need_isr and self.isr3:
+            if self._isr3_prm is None:
+                self._isr3_prm = ops.isr_multi_params(self.isr3, 'rightdown', dev)
+            out['img_self_res'] = ops.isr_multi(r['gray'], self.isr3[0]['val_range'], self._isr3_prm, 3)
+        elif need_isr:
             isr = []
             for b in range(B):   # the shift direction is drawn per sample (cityscapes_ic.py: direct[x % 2][y % 2])
                 d = _DIRECT[xs[b] % 2][ys[b] % 2] if self.shift_type == 'random' else self.shift_type
@@ -207,22 +248,34 @@ class CityscapesICDataset(_SyntheticBase):
             out['img_self_res'] = torch.cat(isr)
         if augment:
             # cityscapes_ic.py:241-261 per sample: sky_mask_transform's draws, then the noise's
-            sky, noise = [], []
+            sky, noise, cow = [], [], []
             for b in range(B):
                 if self.sky_bank is not None:
                     sky.append(ops.draw_sky_mask(self.sky_bank.shape[0], ch, cw, int((labs[b] == 10).sum())))
                 if self.isr_noise:
                     noise.append(ops.draw_isr_noise('noise+blur', source='random'))
+                if self.isr_cow_mask:
+                    cow.append(ops.draw_cow_mask())
             x = out['img_self_res']
             if sky:
                 lab_dev = out['label'] if 'label' in out else _stack_dev(labs, dev)
                 prm, rows, cols = (t.to(dev) for t in ops.sky_mask_params(sky))
                 x = ops.sky_mask(lab_dev, x, self.sky_bank, prm, rows, cols, k_host=[d['k'] for d in sky])
-            if noise:
+            if noise and self.isr3:
+                # randn_like on [3,H,W]: a field of its own per channel -- every channel is a sample of the [B*3,1,H,W] view
+                prm = ops.isr_noise_params(noise).repeat_interleave(3, 0).to(dev)
+                x = ops.isr_noise(x.view(B * 3, 1, ch, cw), prm, 'noise+blur', seed=self.isr_noise_seed,
+                                  offset=self._isr_noise_calls).view(B, 3, ch, cw)
+                self._isr_noise_calls += 1
+            elif noise:
                 x = ops.isr_noise(x, ops.isr_noise_params(noise).to(dev), 'noise+blur', seed=self.isr_noise_seed,
                                   offset=self._isr_noise_calls)
                 self._isr_noise_calls += 1
-            out['img_self_res'], self.last_isr_draws = x, dict(sky=sky or None, isr_noise=noise or None)
+            if cow:
+                taps, tf = (t.to(dev) for t in ops.cow_mask_params(cow))
+                x = ops.cow_mask(x, taps, tf, seed=self.isr_noise_seed, offset=self._cow_calls)
+                self._cow_calls += 1
+            out['img_self_res'], self.last_isr_draws = x, dict(sky=sky or None, isr_noise=noise or None, cow=cow or None)
         return out
 
     def sample_class_stats(self, n=256):
@@ -336,7 +389,9 @@ class DSECDataset(_SyntheticBase):
 class DarkZurichICDataset(_SyntheticBase):
     """mmseg/datasets/dark_zurich_ic.py:21-330 (target of configs/fusion/cs2dz_image+raw-isr_b5.py): outputs ⊆ {'image',
     'night_isr', 'label'}; resize 1920x1080 -> image_resize_size, ISR of the RESIZED frame, then the same random crop / flip for
-    both (train) or the whole resized frame + label (test)."""
+    both (train) or the whole resized frame + label (test).  `shift_3_channel=True` (the preset of `dz_isr_data_type`,
+    dark_zurich_ic.py:110-121) or `isr_parms` as a list of three dicts selects the three-channel ISR: one `ops.isr_multi` call per
+    batch over the whole resized frame, the per-sample crop / flip as its output window; direction 'rightdown', as there."""
 
     def __init__(self, dataset_path='', image_resize_size=(960, 540), image_crop_size=(512, 512), image_resize_size2=None,
                  test_mode=False, split_train=False, dz_isr_data_type='night', shift_pixel=3, enforce_3_channels=True,
@@ -344,11 +399,16 @@ class DarkZurichICDataset(_SyntheticBase):
                  high_resolution_isr=False, isr_parms='', shift_3_channel=False, shift_type='rightdown', synthetic_length=2416,
                  raw_size=(1920, 1080), seed=2, device=None):
         _warn_synthetic(type(self), dataset_path)
-        assert image_resize_size2 is None and not (auto_threshold or high_resolution_isr or shift_3_channel or submit_to_website)
+        assert image_resize_size2 is None and not (auto_threshold or high_resolution_isr or submit_to_website)
+        assert dz_isr_data_type in {'night', 'new_night'}
+        is_list = isinstance(isr_parms, (list, tuple))
+        assert not (shift_3_channel and isr_parms != ''), 'shift_3_channel picks its own parameters: give it or isr_parms, not both'
+        self.isr3 = check_isr3(isr_parms) if is_list else (check_isr3(ISR3_PRESETS[dz_isr_data_type]) if shift_3_channel else None)
+        self._isr3_prm = None
         self.image_resize_size, self.image_crop_size = tuple(image_resize_size), tuple(image_crop_size)
         self.test_mode, self.outputs = test_mode, set(outputs)
         self.CLASSES, self.PALETTE = classes, palette
-        self.isr_parms = dict(isr_parms) if isr_parms != '' else dict(_DEFAULT_ISR, shift_pixel=shift_pixel)
+        self.isr_parms = dict(_DEFAULT_ISR, shift_pixel=shift_pixel) if (isr_parms == '' or is_list) else dict(isr_parms)
         self.shift_type, self.enforce_3_channels = shift_type, enforce_3_channels
         self.length, self.raw_size, self.seed, self.device = synthetic_length, tuple(raw_size), seed, _device(device)
 
@@ -379,7 +439,17 @@ class DarkZurichICDataset(_SyntheticBase):
         else:
             samp = pl.make_samp(B, dev, out_x0=xs, out_y0=ys, flip_out=flips)
             out['image'] = pl.pil_resize_u8(frames, samp, (W, H), (rw, rh), (cw, ch), norm=(pl.IMAGENET_MEAN, pl.IMAGENET_STD))['f']
-        if 'night_isr' in self.outputs:
+        if 'night_isr' in self.outputs and self.isr3:
+            if self._isr3_prm is None:
+                self._isr3_prm = ops.isr_multi_params(self.isr3, 'rightdown', dev)
+            vr = self.isr3[0]['val_range']
+            if self.test_mode:
+                out['night_isr'] = ops.isr_multi(full['gray'], vr, self._isr3_prm, 3)
+            else:   # the ISR of the whole resized frame, cropped and flipped per sample (:252-256) by the kernel's output window
+                wins = [(x, y, f) for x, y, f in zip(xs, ys, flips)]
+                out['night_isr'] = ops.isr_multi(full['gray'], vr, self._isr3_prm, 3, window=torch.tensor(wins, dtype=torch.int32).to(dev),
+                                                 out_size=(ch, cw), window_host=wins)
+        elif 'night_isr' in self.outputs:
             isr = []
             for b in range(B):
                 d = _DIRECT[xs[b] % 2][ys[b] % 2] if (self.shift_type == 'random' and not self.test_mode) else \

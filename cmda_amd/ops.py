@@ -1285,3 +1285,128 @@ def isr_noise(isr, prm, mode, fields=None, seed=0, offset=0, offset_dev=None, en
          c_i32(W), c_i32(int('blur' in mode)), c_i32(int('noise' in mode)), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), off, offd,
          stream_of(isr))
     return out
+
+
+# ---- multi-parameter ISR and cow mask (isr_multi.hip, cow_mask.hip, include/cmda_hip_ext4.h) ----------------------------------------
+ISR_MULTI_ROW = 12   # int32 words per parameter row (CMDAX4_ISR_ROW)
+_ROOT_2, _ROOT_2_PI = 1.4142135623730951, 2.5066282746310002   # datasets/utils.py's constants (math.sqrt)
+
+
+def _isr_multi_rows(parms):
+    """list of dicts (the reference's spelling: val_range, _threshold, _clip_range, shift_pixel) or of (threshold, clip_range,
+    shift_pixel) tuples -> (val_range or None, [(threshold, clip_range, shift_pixel)])"""
+    ranges, rows = set(), []
+    for p in parms:
+        if isinstance(p, dict):
+            ranges.add((float(p['val_range'][0]), float(p['val_range'][1])))
+            rows.append((p['_threshold'], p['_clip_range'], int(p['shift_pixel'])))
+        else:
+            rows.append((p[0], p[1], int(p[2])))
+    assert len(ranges) <= 1, f'isr_multi: one value range per call, got {sorted(ranges)}'
+    return (ranges.pop() if ranges else None), rows
+
+
+def isr_multi_params(parms, shift_direction, device, val_range=None):
+    """The DEVICE parameter table of `isr_multi`: int32 [C,12], one row per channel.  parms: 1..3 (threshold, clip_range,
+    shift_pixel) tuples under the one `val_range`, or the reference's dicts (then `val_range` is taken from them).  Threshold and
+    clip range are scaled by the log span exactly as `isr_from_gray` scales them.  Build it once, outside any capture."""
+    vr, rows = _isr_multi_rows(parms)
+    val_range = vr if val_range is None else val_range
+    assert val_range is not None, 'isr_multi_params: val_range is needed with tuple rows'
+    assert 1 <= len(rows) <= 3, f'isr_multi: 1..3 channels, got {len(rows)}'
+    span = np.log(val_range[1]) - np.log(val_range[0])
+    prm = torch.zeros(len(rows), ISR_MULTI_ROW, dtype=torch.int32)
+    for c, (thr, clip, shift) in enumerate(rows):
+        dirs = isr_dirs(shift_direction, shift)
+        prm[c, 0:2] = _f32_bits([float(np.float32(span * thr)), float(np.float32(span * clip))])
+        prm[c, 2] = len(dirs)
+        prm[c, 3:3 + 2 * len(dirs)] = torch.tensor(dirs, dtype=torch.int32).flatten()
+    return prm.to(device)
+
+
+def isr_multi(gray, val_range, prm_dev, C, window=None, out_size=None, ndir_host=None, window_host=None):
+    """C ISR channels of the uint8 gray maps [B,H,W] in one call (three launches): channel c = `isr_from_gray` with row c of
+    `prm_dev` (`isr_multi_params`), bit for bit -> fp32 [B,C,OH,OW].  window: optional DEVICE int32 [B,3] rows (x0, y0, flip) with
+    out_size = (OH, OW): only that crop of the full result (mirrored when flip) is written; the min / max normalisation stays over the
+    whole map.  ndir_host (C ints) / window_host (B rows): the table values as the host knows them, checked before anything is
+    launched (the device copies cannot be read without a sync; the kernels clamp them)."""
+    check_dev(gray, prm_dev, window)
+    B, H, W = gray.shape
+    assert gray.dtype == torch.uint8 and prm_dev.dtype == torch.int32 and prm_dev.numel() >= C * ISR_MULTI_ROW
+    OH, OW = (H, W) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    if window is not None:
+        assert window.dtype == torch.int32 and window.shape == (B, 3)
+    mm = torch.empty(B * max(C, 0) * 16, dtype=torch.int32, device=gray.device)
+    out = torch.empty(B, max(C, 0), OH, OW, dtype=torch.float32, device=gray.device)
+    nd = (ctypes.c_int * len(ndir_host))(*[int(v) for v in ndir_host]) if ndir_host is not None else None
+    wh = None
+    if window_host is not None:
+        flat = [int(v) for row in window_host for v in row]
+        wh = (ctypes.c_int * len(flat))(*flat)
+    call('cmdax4_isr_multi', ptr(gray), ptr(isr_lut(val_range, gray.device)), ptr(prm_dev), ptr(window), ptr(mm), ptr(out), nd, wh,
+         c_i32(B), c_i32(C), c_i32(H), c_i32(W), c_i32(OH), c_i32(OW), stream_of(gray))
+    return out
+
+
+def draw_cow_mask(prop_range=(0.7, 0.7), log_sigma_range=(float(np.log(16)), float(np.log(17))), max_sigma=16):
+    """The host decisions of ONE cow_masks call of the loader (datasets/utils.py:174-176 with cityscapes_ic.py:264-265's ranges),
+    from torch's CPU generator exactly as the reference consumes it: torch.randn([1]).uniform_(...) twice.  The noise field is NOT
+    drawn here (the reference takes it from np.random.normal): the kernel generates its own.  -> dict(p, sigma, max_sigma)."""
+    p = torch.randn([1, ]).uniform_(prop_range[0], prop_range[1])
+    sigma = torch.exp(torch.randn([1, ]).uniform_(log_sigma_range[0], log_sigma_range[1]))
+    return dict(p=p.item(), sigma=sigma.item(), max_sigma=max_sigma)
+
+
+def cow_mask_params(draws, half_width=None):
+    """list of draw_cow_mask dicts -> CPU (taps fp32 [B,K], tf fp32 [B]): gaussian_kernels' unnormalised Gaussians
+    (utils.py:155-168) and the threshold factors erfinv(2p - 1) * sqrt 2 (:175), both in torch fp32 as the reference computes them.
+    K = 2 * half_width + 1; half_width defaults to the reference's round(max_sigma * 3) * 2 + 1 (97 for max_sigma 16: K = 195)."""
+    max_sigma = draws[0]['max_sigma']
+    assert all(d['max_sigma'] == max_sigma for d in draws)
+    p = torch.tensor([d['p'] for d in draws], dtype=torch.float32)
+    sigmas = torch.tensor([d['sigma'] for d in draws], dtype=torch.float32)[:, None]
+    tf = torch.erfinv(2 * p - 1) * _ROOT_2
+    size = round(max_sigma * 3) * 2 + 1 if half_width is None else int(half_width)
+    x = torch.arange(-size, size + 1)[None, :].float()
+    y = torch.exp(-0.5 * x ** 2 / sigmas ** 2)
+    return (y / (sigmas * _ROOT_2_PI)).contiguous(), tf
+
+
+def _seed64(seed):
+    return ctypes.c_uint64(int(seed) & (2 ** 64 - 1))
+
+
+def cow_field(B, H, W, seed, offset=0, device=None, offset_dev=None):
+    """fp32 [B,H,W]: the noise field `cow_mask` generates for (seed, offset [+ the DEVICE int64 offset_dev]) -- field 3 of the
+    stream whose fields 0..2 are `randn_fields`"""
+    check_dev(offset_dev)
+    dev = offset_dev.device if offset_dev is not None else torch.device(device if device is not None else ('cpu' if L.emulated() else 'cuda'))
+    out = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    off, offd = _offset_args(offset, offset_dev)
+    call('cmdax4_cow_field', ptr(out), c_i32(B), c_i32(H), c_i32(W), _seed64(seed), off, offd, stream_of(out))
+    return out
+
+
+def cow_mask(isr, taps, tf, field=None, seed=0, offset=0, offset_dev=None, enable=None, out=None, debug=False):
+    """isr * cow_masks(...) for the fp32 NCHW [B,C,H,W] ISR (three launches, no host sync): a noise field per sample -- `field`
+    fp32 [B,H,W], or generated in the kernel as `cow_field(seed, offset)` -- blurred with the sample's K taps behind reflect padding
+    and thresholded at tf * std + mean of the blurred field; the same mask on all C channels.  taps fp32 [B,K] / tf fp32 [B]: DEVICE
+    tensors (`cow_mask_params`); enable: optional DEVICE int32 [B] (0 = the sample passes through bit for bit).  Out of place unless
+    `out` is given (`out=isr` is allowed).  debug: also return the blurred field fp32 [B,H,W]."""
+    check_dev(isr, taps, tf, field, offset_dev, enable, out)
+    B, C, H, W = isr.shape
+    assert isr.dtype == torch.float32 and taps.dtype == torch.float32 and tf.dtype == torch.float32
+    assert taps.dim() == 2 and taps.shape[0] == B and tf.shape == (B,)
+    assert enable is None or (enable.dtype == torch.int32 and enable.numel() == B)
+    K = taps.shape[1]
+    if field is not None:
+        assert field.shape == (B, H, W) and field.dtype == torch.float32
+    if out is None:
+        out = torch.empty_like(isr)
+    assert out.shape == isr.shape and out.dtype == torch.float32
+    smooth = torch.empty(B, H, W, dtype=torch.float32, device=isr.device) if debug else None
+    ws = torch.empty(max(1, L.lib().cmdax4_cow_mask_ws_bytes(B, H, W, K)) // 8 + 1, dtype=torch.float64, device=isr.device)
+    off, offd = _offset_args(offset, offset_dev)
+    call('cmdax4_cow_mask', ptr(isr), ptr(out), ptr(taps), ptr(tf), ptr(field), ptr(enable), ptr(smooth), ptr(ws), c_i32(B), c_i32(C),
+         c_i32(H), c_i32(W), c_i32(K), _seed64(seed), off, offd, stream_of(isr))
+    return (out, smooth) if debug else out

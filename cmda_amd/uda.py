@@ -160,8 +160,19 @@ class DACS(nn.Module):
         self.isr_noise_seed = torch.initial_seed() & (2 ** 63 - 1)
         self.mixed_image_to_mixed_isr = bool(cfg.get('mixed_image_to_mixed_isr'))
         self.isr_parms = {'val_range': (1, 10 ** 2), '_threshold': 0.04, '_clip_range': 0.2, 'shift_pixel': 3}
-        if cfg.get('isr_parms'):
+        # three-channel ISR of the mixed image: the flag (dacs.py:159-165, the 'dacs' preset) or `isr_parms` as a list of three dicts
+        # under one value range; the flag together with isr_parms is refused as there (:167-168)
+        self.isr3 = None
+        if cfg.get('shift_3_channel'):
+            assert not cfg.get('isr_parms'), 'shift_3_channel picks its own parameters: give it or isr_parms, not both'
+            from .datasets import ISR3_PRESETS
+            self.isr3 = [dict(p) for p in ISR3_PRESETS['dacs']]
+        elif isinstance(cfg.get('isr_parms'), (list, tuple)):
+            from .datasets import check_isr3
+            self.isr3 = check_isr3(cfg['isr_parms'])
+        elif cfg.get('isr_parms'):
             self.isr_parms = dict(cfg['isr_parms'])
+        assert not (self.isr3 and self.image_only), 'a three-channel ISR acts on the mixed ISR: the image-only train types have none'
         # (the reference recomputes the ISR of the mixed image for its ISR types only, dacs.py:727; the image-only types have none)
         assert self.image_only or self.mixed_image_to_mixed_isr, 'configs/fusion/* recompute the ISR from the mixed image'
         self.isr_another_fusion = bool(cfg.get('isr_another_fusion'))
@@ -424,6 +435,8 @@ class DACS(nn.Module):
             return d
         self._ctl = dict(key=key, hosts=hosts, hviews=[views(h) for h in hosts], events=[None] * nring, slot=0, dev=devbuf,
                          d=views(devbuf), kx=kx, ky=ky)
+        if self.isr3:   # a constant of the configuration: uploaded here, once, never inside a captured region
+            self._ctl['d']['isr3_prm'] = ops.isr_multi_params(self.isr3, 'rightdown', dev)
         return self._ctl
 
     def _stage(self, cb, draws):
@@ -624,8 +637,11 @@ class DACS(nn.Module):
             """the mixed image and its ISR (dacs.py:716-771)"""
             mixed_img = self._mixed_image(day_image, night_image, lab, classes, ctl)
             gray = ops.isr_gray(mixed_img)
-            mixed_isr = ops.isr_from_gray(gray, self.isr_parms['val_range'], self.isr_parms['_threshold'],
-                                          self.isr_parms['_clip_range'], self.isr_parms['shift_pixel'], direction, dirs_dev=ctl['dirs'])
+            if self.isr3:   # dacs.py:745-752: three parameter rows, direction 'rightdown' whatever shift_type says
+                mixed_isr = ops.isr_multi(gray, self.isr3[0]['val_range'], ctl['isr3_prm'], 3)
+            else:
+                mixed_isr = ops.isr_from_gray(gray, self.isr_parms['val_range'], self.isr_parms['_threshold'],
+                                              self.isr_parms['_clip_range'], self.isr_parms['shift_pixel'], direction, dirs_dev=ctl['dirs'])
             if self.isr_noise_dacs_type:   # dacs.py:753-755: channel 0 through add_noise_on_isr, the result on all three channels
                 mixed_isr = ops.isr_noise(mixed_isr, ctl['noise_prm'], self.isr_noise_dacs_type, seed=self.isr_noise_seed,
                                           offset_dev=ctl['offset'])
