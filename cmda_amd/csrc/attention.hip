@@ -31,16 +31,23 @@ struct AttnParams {
 };
 
 // queries per block of the forward-shaped kernels: 64 (one pass of 4 waves x 16) or 128 (two passes, K/V loaded once for
-// both) -- the launcher takes 64 while that still leaves the grid under ~4 blocks per CU (stage 3: 27.4 -> 22.9 us)
-static inline int fwd_queries_per_block(int B, int N, int heads) {
-  return (long)((N + 127) / 128) * heads * B < 1024 ? 64 : 128;
+// both) -- the launcher takes 64 while that still leaves the grid under ~4 blocks per CU (stage 3: 27.4 -> 22.9 us).
+// The full-key instances' passes are half as long, so the K / V fill weighs more: they take 128 from 512 blocks of 128 up, the grid
+// that fills the 512 block slots of the chip once (graph-timed forward, 64 | 128 per block: 512 blocks of 128 11.6 | 9.9 and
+// 10.5 | 9.2 us, 320 blocks 9.5 | 8.8, 256 blocks 6.5 | 7.4 and 6.1 | 7.0; profiles/attn_fullkeys_bench.txt)
+static inline int fwd_queries_per_block(int B, int N, int heads, bool full = false) {
+  return (long)((N + 127) / 128) * heads * B < (full ? 512 : 1024) ? 64 : 128;
 }
 
 // MAXK: keys held in LDS -- 256 (every stage of a 512 x 512 crop; two blocks per CU) or 320 (inference on 440 x 640 frames,
-// encoder_decoder.py:897-936: 260 / 280 keys after the spatial reduction; forward only, one block per CU)
-template <int MAXK>
+// encoder_decoder.py:897-936: 260 / 280 keys after the spatial reduction; forward only, one block per CU).
+// FULL: Nk == MAXK and scale > 0 (every training launch: 256 keys at every stage) -- the full-key form of attention_common.h: no key
+// mask (64 compares + selects per lane and the SGPR spills of their lane masks), no tile guards, unnormalised probabilities into the
+// second GEMM and 1 / l applied to the 16 outputs.  The masked form serves every other key count and is the reference for it.
+template <int MAXK, bool FULL = false>
 __global__ __launch_bounds__(256, MAXK <= 256 ? 2 : 1) void attn_fwd_kernel(AttnParams p) {
   constexpr int NT = MAXK / 16;
+  const int Nk = FULL ? MAXK : p.Nk;
   __shared__ __attribute__((aligned(1024))) bf16_t sK[MAXK * kHD];
   __shared__ __attribute__((aligned(1024))) bf16_t sV[MAXK * kHD];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, g = lane >> 4, l15 = lane & 15;
@@ -48,11 +55,11 @@ __global__ __launch_bounds__(256, MAXK <= 256 ? 2 : 1) void attn_fwd_kernel(Attn
   const unsigned lb = xcd_logical_block(), bh = lb / nqb;
   const long qblk = lb - bh * nqb;
   const int h = (int)(bh % (unsigned)p.heads), b = (int)(bh / (unsigned)p.heads);
-  const bf16_t* kbase = p.kv + (long)b * p.Nk * 2 * p.C + h * kHD;
-  load_kv_tile<MAXK>(kbase, 2 * p.C, p.Nk, sK, wid, lane, 4);
-  load_kv_tile<MAXK>(kbase + p.C, 2 * p.C, p.Nk, sV, wid, lane, 4);
+  const bf16_t* kbase = p.kv + (long)b * Nk * 2 * p.C + h * kHD;
+  load_kv_tile<MAXK>(kbase, 2 * p.C, Nk, sK, wid, lane, 4);
+  load_kv_tile<MAXK>(kbase + p.C, 2 * p.C, Nk, sV, wid, lane, 4);
   __syncthreads();
-  const int nt = (p.Nk + 15) >> 4;
+  const int nt = (Nk + 15) >> 4;
   const bf16_t* qb = p.q + (long)b * p.N * p.C + h * kHD;
   bf16_t* ob = p.o + (long)b * p.N * p.C + h * kHD;
   for (int pass = 0; pass < p.q_per_block / 64; ++pass) {
@@ -61,13 +68,15 @@ __global__ __launch_bounds__(256, MAXK <= 256 ? 2 : 1) void attn_fwd_kernel(Attn
     u16x8 qf[2];
     load_qfrag(qb, q0, p.N, p.C, g, l15, qf);
     f32x4 pr[NT];
-    scores_softmax<NT>(sK, qf, nt, p.Nk, p.scale, g, l15, pr);
+    float inv = 1.f;
+    if constexpr (FULL) inv = scores_exp_full<NT>(sK, qf, p.scale, g, l15, pr);
+    else scores_softmax<NT>(sK, qf, nt, Nk, p.scale, g, l15, pr);
     f32x4 oacc[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) oacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < NT / 2; ++u) {
-      if (2 * u < nt) {
+      if (FULL || 2 * u < nt) {
         const u16x8 pb = pack_pair(pr[2 * u], pr[2 * u + 1]);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
@@ -77,6 +86,7 @@ __global__ __launch_bounds__(256, MAXK <= 256 ? 2 : 1) void attn_fwd_kernel(Attn
     if (q0 + l15 < p.N) {
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
+        if constexpr (FULL) oacc[dt] *= inv;
         const float v[4] = {oacc[dt][0], oacc[dt][1], oacc[dt][2], oacc[dt][3]};
         st4(ob + (q0 + l15) * p.C + 16 * dt + 4 * g, v);
       }
@@ -110,19 +120,25 @@ struct AttnBwdParams {
   int spans;            // query spans of the dK/dV kernel
 };
 
+// FULL: Nk == kMaxK and scale > 0, the full-key form (attn_fwd_kernel).  With e = l P the unnormalised exponentials and inv = 1 / l:
+//   D = inv * sum_k e dP,   dS^T = (scale inv) e (dP - D),   and since dQ^T = K^T dS^T is linear in dS the factor scale * inv is applied
+//   to the 16 dQ accumulators, not to the 64 dS values: what is packed for the last GEMM is e (dP - D).
+// stats[b, h, q, 2] = (lse of the scaled scores, D) is the same contract with attn_bwd_dkv_kernel in both forms.
+template <bool FULL = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
   __shared__ __attribute__((aligned(1024))) bf16_t sK[kMaxK * kHD];
   __shared__ __attribute__((aligned(1024))) bf16_t sV[kMaxK * kHD];
+  const int Nk = FULL ? kMaxK : p.Nk;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, g = lane >> 4, l15 = lane & 15;
   const unsigned nqb = (unsigned)((p.N + p.fwd_q_per_block - 1) / p.fwd_q_per_block);
   const unsigned lb = xcd_logical_block(), bh = lb / nqb;
   const long qblk = lb - bh * nqb;
   const int h = (int)(bh % (unsigned)p.heads), b = (int)(bh / (unsigned)p.heads);
-  const bf16_t* kbase = p.kv + (long)b * p.Nk * 2 * p.C + h * kHD;
-  load_kv_tile(kbase, 2 * p.C, p.Nk, sK, wid, lane, 4);
-  load_kv_tile(kbase + p.C, 2 * p.C, p.Nk, sV, wid, lane, 4);
+  const bf16_t* kbase = p.kv + (long)b * Nk * 2 * p.C + h * kHD;
+  load_kv_tile(kbase, 2 * p.C, Nk, sK, wid, lane, 4);
+  load_kv_tile(kbase + p.C, 2 * p.C, Nk, sV, wid, lane, 4);
   __syncthreads();
-  const int nt = (p.Nk + 15) >> 4;
+  const int nt = (Nk + 15) >> 4;
   const long rowb = (long)b * p.N;
   const bf16_t* qb = p.q + rowb * p.C + h * kHD;
   const bf16_t* dob = p.d_o + rowb * p.C + h * kHD;
@@ -135,13 +151,14 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
     load_qfrag(qb, q0, p.N, p.C, g, l15, qf);
     load_qfrag(dob, q0, p.N, p.C, g, l15, dof);
     f32x4 pr[kNT], dp[kNT];
-    float lse;
-    scores_softmax(sK, qf, nt, p.Nk, p.scale, g, l15, pr, &lse);
+    float lse, inv = 1.f;
+    if constexpr (FULL) inv = scores_exp_full(sK, qf, p.scale, g, l15, pr, &lse);
+    else scores_softmax(sK, qf, nt, Nk, p.scale, g, l15, pr, &lse);
     float dsum = 0.f;
 #pragma unroll
     for (int t = 0; t < kNT; ++t) {
       dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (t < nt) {
+      if (FULL || t < nt) {
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) dp[t] = mfma_bf16_16x16x32(frag_rows(sV, 16 * t, kk, g, l15), dof[kk], dp[t]);
       }
@@ -149,16 +166,20 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
       for (int r = 0; r < 4; ++r) dsum += pr[t][r] * dp[t][r];
     }
     dsum = col_sum(dsum);
+    if constexpr (FULL) dsum *= inv;
 #pragma unroll
     for (int t = 0; t < kNT; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) dp[t][r] = p.scale * pr[t][r] * (dp[t][r] - dsum);  // dS^T
+      for (int r = 0; r < 4; ++r) {
+        if constexpr (FULL) dp[t][r] = pr[t][r] * (dp[t][r] - dsum);  // dS^T / (scale inv)
+        else dp[t][r] = p.scale * pr[t][r] * (dp[t][r] - dsum);       // dS^T
+      }
     f32x4 dqacc[4];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) dqacc[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < kNT / 2; ++u) {
-      if (2 * u < nt) {
+      if (FULL || 2 * u < nt) {
         const u16x8 db = pack_pair(dp[2 * u], dp[2 * u + 1]);
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt)
@@ -168,6 +189,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(AttnBwdParams p) {
     if (q0 + l15 < p.N) {
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt) {
+        if constexpr (FULL) dqacc[dt] *= p.scale * inv;
         const float v[4] = {dqacc[dt][0], dqacc[dt][1], dqacc[dt][2], dqacc[dt][3]};
         st4(dqb + (q0 + l15) * p.C + 16 * dt + 4 * g, v);
       }
@@ -745,6 +767,10 @@ static inline bool head_dim_ok(int heads, int C) {
   return C == heads * hd && hd % kHD == 0 && hd >= kHD && hd <= 1024;
 }
 
+// the full-key instances (attn_fwd_kernel<256, true>, attn_bwd_dq_kernel<true>) take the launch when every one of the 256 key rows is
+// live and the scale is positive (they take the row max over the raw scores); everything else -- a NaN scale too -- stays masked
+static inline bool attn_full_keys(int Nk, float scale) { return Nk == kMaxK && scale > 0.f; }
+
 // q [B*N, C] bf16, kv [B*Nk, 2C] bf16 -> o [B*N, C] bf16; head_dim = C / heads in {64, 128, ..., 1024}, Nk <= 320 (the backward: 256).
 extern "C" int cmda_attention_fwd(const void* q, const void* kv, void* o, int B, int N, int Nk, int heads, int C,
                                   float scale, int dtype, void* stream) {
@@ -753,12 +779,14 @@ extern "C" int cmda_attention_fwd(const void* q, const void* kv, void* o, int B,
   if (heads <= 0 || Nk <= 0 || Nk > kMaxKFwd || !head_dim_ok(heads, C)) return CMDA_ERR_UNSUPPORTED;
   if (heads > 65535 || B > 65535) return CMDA_ERR_SHAPE;
   if (C != heads * kHD) return attn_wide_fwd(q, kv, o, B, N, Nk, heads, C, scale, stream);
-  const int qpb = fwd_queries_per_block(B, N, heads);
+  const bool full = attn_full_keys(Nk, scale);
+  const int qpb = fwd_queries_per_block(B, N, heads, full);
   AttnParams p{(const bf16_t*)q, (const bf16_t*)kv, (bf16_t*)o, B, N, Nk, heads, C, scale, qpb};
   const long nblk = (long)((N + qpb - 1) / qpb) * heads * B;
   if (nblk > 0x7fffffffL) return CMDA_ERR_SHAPE;
   dim3 grid((unsigned)nblk);
-  if (Nk <= kMaxK) CMDA_LAUNCH(attn_fwd_kernel<kMaxK>, grid, dim3(256), 0, stream, p);
+  if (full) CMDA_LAUNCH((attn_fwd_kernel<kMaxK, true>), grid, dim3(256), 0, stream, p);
+  else if (Nk <= kMaxK) CMDA_LAUNCH(attn_fwd_kernel<kMaxK>, grid, dim3(256), 0, stream, p);
   else CMDA_LAUNCH(attn_fwd_kernel<kMaxKFwd>, grid, dim3(256), 0, stream, p);
   CMDA_CHECK_LAUNCH();
 }
@@ -787,13 +815,15 @@ extern "C" int cmda_attention_bwd(const void* q, const void* kv, const void* d_o
   }
   const bool direct = cmda_attention_bwd_direct(B, N, Nk, heads) != 0 && dkv16 != nullptr;
   if (!direct && dkv32 == nullptr) return CMDA_ERR_SHAPE;
-  const int fqpb = fwd_queries_per_block(B, N, heads);
+  const bool full = attn_full_keys(Nk, scale);
+  const int fqpb = fwd_queries_per_block(B, N, heads, full);
   AttnBwdParams p{(const bf16_t*)q, (const bf16_t*)kv, (const bf16_t*)d_o, (bf16_t*)dq, dkv32, direct ? (bf16_t*)dkv16 : nullptr, stats,
                   B, N, Nk, heads, C, 0, scale, fqpb};
   const long nblk1 = (long)((N + fqpb - 1) / fqpb) * heads * B;
   if (nblk1 > 0x7fffffffL) return CMDA_ERR_SHAPE;
   dim3 g1((unsigned)nblk1);
-  CMDA_LAUNCH(attn_bwd_dq_kernel, g1, dim3(256), 0, stream, p);
+  if (full) CMDA_LAUNCH(attn_bwd_dq_kernel<true>, g1, dim3(256), 0, stream, p);
+  else CMDA_LAUNCH(attn_bwd_dq_kernel<false>, g1, dim3(256), 0, stream, p);
   // dK/dV: (batch, head, key slice) x query spans, spans a multiple of 128 queries.  Every span costs one fp32 atomic per
   // dK/dV element (~1.3 TB/s chip-wide: 1280 blocks of the stage-3 shape spent 31 of their 61 us there), so only as many
   // spans as it takes to reach ~2 blocks per CU -- and a single span (direct mode) when the queries are few.

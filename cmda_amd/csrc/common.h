@@ -218,6 +218,13 @@ static inline float fast_rcp(float x) { return 1.0f / x; }
 #else
 static __device__ __forceinline__ float fast_rcp(float x) { return __builtin_amdgcn_rcpf(x); }  // v_rcp_f32 (1 ulp), not the ~10-op IEEE division
 #endif
+// 2^x as the bare v_exp_f32 (1 ulp; no range scaling around it, so a result below 2^-126 flushes to zero -- callers pass x <= ~0
+// and want exactly that); __expf is this plus a multiply by log2(e) that a caller with its own scale factor can fold away
+#ifdef CMDA_EMU
+static inline float fast_exp2(float x) { return exp2f(x); }
+#else
+static __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+#endif
 // returns erf(u) and leaves exp(-u^2) in e (the GELU derivative needs the same exponential for its pdf term)
 static __device__ __forceinline__ float erf_as_e(float u, float& e) {
   const float ax = fabsf(u);

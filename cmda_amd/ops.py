@@ -600,6 +600,14 @@ def attention_fused_fwd(q, kv, B, N, Nk, heads, C, scale):
     return o
 
 
+def attention_fwd_queries_per_block(B, N, heads, Nk=256, scale=0.125):
+    """queries per block of the forward and dQ kernels at head dim 64 (bf16): the rule of fwd_queries_per_block in attention.hip,
+    restated for the tools that label their timings with it (tools/dbg/attn_graph_bench.py) -- the library does not export it.
+    The full-key instances (256 keys, scale > 0) switch to 128 from 512 blocks of 128 up, the masked ones from 1024"""
+    full = int(Nk) == 256 and scale > 0
+    return 64 if -(-int(N) // 128) * int(heads) * int(B) < (512 if full else 1024) else 128
+
+
 def attention_bwd_direct(B, N, Nk, heads):
     """True: the fused backward stores dK | dV straight as bf16 (few queries: one block per key slice walks them all)"""
     return bool(L.lib().cmda_attention_bwd_direct(int(B), int(N), int(Nk), int(heads)))

@@ -26,7 +26,9 @@ def timeit(fn, iters=40, reps=5):
 
 
 bf = torch.bfloat16
-for (B, N, heads) in ((4, 16384, 1), (2, 16384, 1), (4, 4096, 2), (2, 4096, 2), (4, 1024, 5), (2, 1024, 5), (4, 256, 8), (2, 256, 8)):
+# usage: attn_graph_bench.py [batches, default 4,2] -- e.g. 2,4,8 when the queries-per-block rule is re-measured
+batches = [int(x) for x in sys.argv[1].split(',')] if len(sys.argv) > 1 else [4, 2]
+for (B, N, heads) in [(B, N, heads) for (N, heads) in ((16384, 1), (4096, 2), (1024, 5), (256, 8)) for B in batches]:
     C, Nk = heads * 64, 256
     q = torch.randn(B * N, C, device='cuda').to(bf); kv = torch.randn(B * Nk, 2 * C, device='cuda').to(bf); do = torch.randn_like(q)
     direct = ops.attention_bwd_direct(B, N, Nk, heads)
@@ -35,4 +37,5 @@ for (B, N, heads) in ((4, 16384, 1), (2, 16384, 1), (4, 4096, 2), (2, 4096, 2), 
     o = torch.empty_like(q)
     tf = timeit(lambda: ops.attention_fused_fwd(q, kv, B, N, Nk, heads, C, 0.125))
     tb = timeit(lambda: ops.attention_fused_bwd(q, kv, do, dkv32, B, N, Nk, heads, C, 0.125, dkv16=dkv16))
-    print(f'B{B} N{N} heads{heads}: fwd {tf:6.1f} us   bwd (dq + dkv) {tb:6.1f} us  direct={direct}', flush=True)
+    qpb = ops.attention_fwd_queries_per_block(B, N, heads)
+    print(f'B{B} N{N} heads{heads}: fwd {tf:6.1f} us   bwd (dq + dkv) {tb:6.1f} us  direct={direct}  queries/block={qpb}', flush=True)
