@@ -1,5 +1,5 @@
 """ctypes binding of libcmda_hip.so (the C ABI declared in include/cmda_hip.h and its extensions include/cmda_hip_ext.h,
-include/cmda_hip_ext2.h, include/cmda_hip_ext3.h and include/cmda_hip_ext4.h).
+include/cmda_hip_ext2.h, include/cmda_hip_ext3.h, include/cmda_hip_ext4.h and include/cmda_hip_ext5.h).
 
 The product path has exactly one backend: the gfx950 kernel library built in-tree by
 ``__graft_entry__.build()`` / ``make hip``.  If it is missing, or a tensor is not on the GPU,
@@ -24,6 +24,7 @@ ABI_VERSION, ABI_EXT_VERSION = 8, 1
 ABI_EXT2_VERSION = 1
 ABI_EXT3_VERSION = 1
 ABI_EXT4_VERSION = 1
+ABI_EXT5_VERSION = 1
 
 
 class View(ctypes.Structure):
@@ -91,6 +92,16 @@ def _declare(lib):
         raise CmdaError('libcmda_hip.so fourth ABI table (cmdax4_*) version mismatch')
     lib.cmdax4_cow_mask_ws_bytes.restype = ctypes.c_int64
     lib.cmdax4_cow_mask_ws_bytes.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    # the fifth table (include/cmda_hip_ext5.h): batched event prep, ordered voxel grid, batched events_norm
+    if not hasattr(lib, 'cmdax5_abi_version'):
+        raise CmdaError('the kernel library lacks the fifth ABI table (cmdax5_*): rebuild it')
+    lib.cmdax5_abi_version.restype = ctypes.c_int
+    if lib.cmdax5_abi_version() != ABI_EXT5_VERSION:
+        raise CmdaError('libcmda_hip.so fifth ABI table (cmdax5_*) version mismatch')
+    lib.cmdax5_voxel_ordered_ws_bytes.restype = ctypes.c_int64
+    lib.cmdax5_voxel_ordered_ws_bytes.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    lib.cmdax5_events_norm_ws_bytes.restype = ctypes.c_int64
+    lib.cmdax5_events_norm_ws_bytes.argtypes = [ctypes.c_int, ctypes.c_int64]
     return lib
 
 

@@ -293,14 +293,17 @@ class DSECDataset(_SyntheticBase):
     """mmseg/datasets/dsec.py:124-366 (target domain).  Training samples (no 'label' in outputs): random crop `crop_size` of the
     480x640 frame -> random flip -> PIL resize to `after_crop_resize_size`; 'warp_img_self_res' = real-time ISR of the resized
     frame; 'events_vg' = rectified events -> voxel grid (events_bins) -> events_norm -> the same crop / flip -> bilinear -> x3.
-    Test samples ('label' in outputs): the first 440 rows, no augmentation, + 'label' [440,640] and 'img_metas'."""
+    Test samples ('label' in outputs): the first 440 rows, no augmentation, + 'label' [440,640] and 'img_metas'.
+    ordered_events=True takes the event branch of a batch through `pipeline.events_voxel_batch`: an order-preserving voxel grid and
+    a statistics reduction of fixed shape (no float atomics), so 'events_vg' is bit-identical from run to run."""
 
     def __init__(self, dataset_txt_path='', events_num=-1, events_bins=5, events_clip_range=None, crop_size=(400, 400),
                  after_crop_resize_size=(512, 512), image_change_range=1, outputs={'events_vg', 'image'}, output_num=1,
                  classes=CLASSES, palette=PALETTE, isr_shift_pixel=4, test_mode=False, events_bins_5_avg_1=False, isr_parms='',
                  isr_type='real_time', enforce_3_channels=True, shift_type='rightdown', synthetic_length=1692,
-                 synthetic_events=500000, seed=1, device=None):
+                 synthetic_events=500000, seed=1, device=None, ordered_events=False):
         _warn_synthetic(type(self), dataset_txt_path)
+        self.ordered_events = ordered_events
         assert output_num == 1 and not events_bins_5_avg_1 and isr_type == 'real_time'
         assert shift_type in {'all', 'random', 'rightdown'}
         self.outputs = set(outputs)
@@ -333,6 +336,16 @@ class DSECDataset(_SyntheticBase):
         clip = random.uniform(*self.events_clip_range) if self.events_clip_range is not None else (t.numel() - 1) / 500000 * 1.5
         return ops.events_norm(vg, clip)
 
+    def _voxels(self, raws):
+        """normalised voxel grids [B,bins,480,640] of a batch; the clip ranges are drawn in sample order on both paths"""
+        if not self.ordered_events:
+            return torch.stack([self._voxel(r) for r in raws])
+        dev = self.device
+        clips = [random.uniform(*self.events_clip_range) if self.events_clip_range is not None else (r[1].numel() - 1) / 500000 * 1.5
+                 for r in raws]
+        events = [tuple(r[k].to(dev) for k in (1, 2, 3, 4)) for r in raws]
+        return pl.events_voxel_batch(events, self.rectify_map, self.events_bins, 480, 640, clips)
+
     def get_batch(self, indices):
         dev = self.device
         B = len(indices)
@@ -362,7 +375,7 @@ class DSECDataset(_SyntheticBase):
                                                      self.isr_parms['_clip_range'], self.isr_parms['shift_pixel'], d))
                     out['warp_img_self_res'] = torch.cat(isr)
             if 'events_vg' in self.outputs:
-                vg = torch.stack([self._voxel(r) for r in raws])
+                vg = self._voxels(raws)
                 out['events_vg'] = pl.crop_flip_resize_f32(vg, samp, (cw, ch), self.after_crop_resize_size,
                                                            rep=3 if (self.enforce_3_channels and self.events_bins == 1) else 1)
             return out
@@ -372,7 +385,7 @@ class DSECDataset(_SyntheticBase):
             r = pl.pil_resize_u8(frames, samp, (640, 480), (640, 480), norm=(pl.IMAGENET_MEAN, pl.IMAGENET_STD))
             out['warp_image'] = r['f'][:, :, :440].contiguous()
         if 'events_vg' in self.outputs:
-            vg = torch.stack([self._voxel(r) for r in raws])[:, :, :440, :]
+            vg = self._voxels(raws)[:, :, :440, :]
             out['events_vg'] = (vg.repeat(1, 3, 1, 1) if (self.enforce_3_channels and self.events_bins == 1) else vg).contiguous()
         out['label'] = _stack_dev([r[5][:440] for r in raws], dev)
         if 'img_metas' in self.outputs:

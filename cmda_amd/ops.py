@@ -1418,3 +1418,48 @@ def cow_mask(isr, taps, tf, field=None, seed=0, offset=0, offset_dev=None, enabl
     call('cmdax4_cow_mask', ptr(isr), ptr(out), ptr(taps), ptr(tf), ptr(field), ptr(enable), ptr(smooth), ptr(ws), c_i32(B), c_i32(C),
          c_i32(H), c_i32(W), c_i32(K), _seed64(seed), off, offd, stream_of(isr))
     return (out, smooth) if debug else out
+
+
+# ---- ordered event voxel grid and batched events_norm (voxel_ordered.hip, include/cmda_hip_ext5.h) ------------------------------------
+def sample_offsets(offsets):
+    """sample offsets (B + 1 ints, host) -> (ctypes int64 array, B)"""
+    offs = [int(v) for v in offsets]
+    return (ctypes.c_int64 * len(offs))(*offs), len(offs) - 1
+
+
+def events_voxel_ordered_batch(t, x, y, pol, offsets, bins, H, W):
+    """events_to_voxel_grid for B samples, order-preserving: prepared fp32 events concatenated over the batch, `offsets` the B + 1
+    host sample boundaries -> fp32 [B,bins,H,W].  Every cell is the sequential fp32 sum of the reference (corner pass, then event
+    index): bit-identical to its CPU result and from run to run.  No float atomics; the launch count does not depend on B."""
+    check_dev(t, x, y, pol)
+    assert t.dtype == x.dtype == y.dtype == pol.dtype == torch.float32
+    offs, B = sample_offsets(offsets)
+    n_total = t.numel()
+    assert B < 1 or offs[B] <= n_total == x.numel() == y.numel() == pol.numel(), 'offsets run past the event arrays'
+    grid = torch.empty(max(B, 0), max(bins, 0), max(H, 0), max(W, 0), dtype=torch.float32, device=t.device)
+    ws = torch.empty(max(1, L.lib().cmdax5_voxel_ordered_ws_bytes(B, offs[B] if B >= 1 else 0, bins, H, W)) // 8 + 1,
+                     dtype=torch.float64, device=t.device)
+    call('cmdax5_voxel_ordered', ptr(t), ptr(x), ptr(y), ptr(pol), offs, ptr(grid), ptr(ws), c_i32(B), c_i32(bins), c_i32(H),
+         c_i32(W), stream_of(t))
+    return grid
+
+
+def events_to_voxel_grid_ordered(t, x, y, pol, bins, H, W):
+    """`events_to_voxel_grid` with the reference's summation order (one sample): fp32 [bins,H,W], bit-identical to the oracle"""
+    return events_voxel_ordered_batch(t, x, y, pol, [0, t.numel()], bins, H, W)[0]
+
+
+def events_norm_batch(grids, clip_ranges, final_range=1.0):
+    """`events_norm` on each of the B grids fp32 [B,...] with its own clip range (B host floats), three launches; the statistics
+    are reduced in a fixed shape (no float atomics): the result is bit-identical from run to run."""
+    check_dev(grids)
+    assert grids.dtype == torch.float32
+    B = grids.shape[0]
+    n = grids[0].numel() if B else 0
+    assert len(clip_ranges) == B
+    out = torch.empty_like(grids)
+    ws = torch.empty(max(1, L.lib().cmdax5_events_norm_ws_bytes(B, n)) // 8 + 1, dtype=torch.float64, device=grids.device)
+    clips = (ctypes.c_float * max(B, 1))(*[float(c) for c in clip_ranges])
+    call('cmdax5_events_norm_batch', ptr(grids), ptr(out), ptr(ws), c_i32(B), c_i64(n), clips, c_f32(final_range),
+         stream_of(grids))
+    return out

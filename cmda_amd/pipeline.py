@@ -148,6 +148,33 @@ def event_prep(t, x, y, p, rect_map=None, H=480, W=640):
     return outs
 
 
+def event_prep_batch(t, x, y, p, offsets, rect_map=None, H=480, W=640):
+    """`event_prep` for B samples in one launch: the raw events concatenated over the batch, `offsets` the B + 1 host sample
+    boundaries; every sample is normalised by its own first / last time stamp -> (t_norm, x_rect, y_rect, pol) fp32 [n_total]"""
+    check_dev(t, x, y, p, rect_map)
+    assert t.dtype == torch.int64 and x.dtype == torch.int32 and y.dtype == torch.int32 and p.dtype == torch.uint8
+    offs, B = ops.sample_offsets(offsets)
+    N = t.numel()
+    assert B < 1 or offs[B] <= N == x.numel() == y.numel() == p.numel(), 'offsets run past the event arrays'
+    assert rect_map is None or rect_map.numel() == H * W * 2
+    outs = [torch.empty(N, dtype=torch.float32, device=t.device) for _ in range(4)]
+    call('cmdax5_event_prep_batch', ptr(t), ptr(x), ptr(y), ptr(p), offs, c_i32(B), ptr(rect_map), c_i32(H), c_i32(W),
+         *[ptr(o) for o in outs], stream_of(t))
+    return outs
+
+
+def events_voxel_batch(events, rect_map, bins, H, W, clip_ranges):
+    """dsec.py:341-366 for a batch, bit-reproducible: events = list of B raw tuples (t i64, x i32, y i32, p u8), clip_ranges = B
+    host floats -> normalised voxel grids fp32 [B,bins,H,W].  One concatenation per field, then three ABI calls for the whole
+    batch: batched prep, the order-preserving voxel grid (bit-identical to the reference's CPU sum), the batched events_norm."""
+    offsets = [0]
+    for ev in events:
+        offsets.append(offsets[-1] + ev[0].numel())
+    t, x, y, p = (torch.cat([ev[k] for ev in events]) for k in range(4))
+    tn, xr, yr, pol = event_prep_batch(t, x, y, p, offsets, rect_map, H, W)
+    return ops.events_norm_batch(ops.events_voxel_ordered_batch(tn, xr, yr, pol, offsets, bins, H, W), clip_ranges)
+
+
 def crop_flip_resize_f32(x, samp, crop, out_size, rep=1):
     """x fp32 [B,C,IH,IW]; crop = (w, h) window at samp.src_*; bilinear (align_corners=False) to out_size = (w, h)"""
     check_dev(x, samp)
@@ -160,10 +187,12 @@ def crop_flip_resize_f32(x, samp, crop, out_size, rep=1):
 
 # ------------------------------------------------------------------------------------------------------------ composed pipelines
 def dsec_target_sample(warp_u8, events, rect_map, x0, y0, flip, isr_parms, shift_direction='rightdown', crop=(400, 400),
-                       out_size=(512, 512), events_bins=1, events_clip_range=None):
+                       out_size=(512, 512), events_bins=1, events_clip_range=None, ordered_events=False):
     """One batch of DSEC training samples (dsec.py:189-339 with outputs {'warp_image', 'events_vg', 'warp_img_self_res'},
     isr_type 'real_time', enforce_3_channels): warp_u8 uint8 [B,480,640,3]; events = list of B tuples (t i64, x i32, y i32, p u8);
-    x0 / y0 / flip: per-sample crop origin and flip flag (the loader's random draws).  Returns the reference's target dict."""
+    x0 / y0 / flip: per-sample crop origin and flip flag (the loader's random draws).  ordered_events: the event branch through
+    `events_voxel_batch` (order-preserving voxel grid, no float atomics: events_vg is bit-reproducible) instead of the per-sample
+    chain.  Returns the reference's target dict."""
     B = warp_u8.shape[0]
     dev = warp_u8.device
     samp = make_samp(B, dev, src_x0=x0, src_y0=y0, flip_src=flip)
@@ -171,14 +200,16 @@ def dsec_target_sample(warp_u8, events, rect_map, x0, y0, flip, isr_parms, shift
     isr = ops.isr_from_gray(r['gray'], isr_parms['val_range'], isr_parms['_threshold'], isr_parms['_clip_range'],
                             isr_parms['shift_pixel'], shift_direction)
     H, W = warp_u8.shape[1], warp_u8.shape[2]
-    grids = []
-    for (t, x, y, p) in events:
-        tn, xr, yr, pol = event_prep(t, x, y, p, rect_map, H, W)
-        g = ops.events_to_voxel_grid(tn, xr, yr, pol, events_bins, H, W)
-        n = t.numel()
-        clip = events_clip_range if events_clip_range is not None else (n - 1) / 500000 * 1.5
-        grids.append(ops.events_norm(g, clip))
-    vg = torch.stack(grids)                                           # [B,bins,480,640]
+    clips = [events_clip_range if events_clip_range is not None else (ev[0].numel() - 1) / 500000 * 1.5 for ev in events]
+    if ordered_events:
+        vg = events_voxel_batch(events, rect_map, events_bins, H, W, clips)
+    else:
+        grids = []
+        for (t, x, y, p), clip in zip(events, clips):
+            tn, xr, yr, pol = event_prep(t, x, y, p, rect_map, H, W)
+            g = ops.events_to_voxel_grid(tn, xr, yr, pol, events_bins, H, W)
+            grids.append(ops.events_norm(g, clip))
+        vg = torch.stack(grids)                                       # [B,bins,480,640]
     ev = crop_flip_resize_f32(vg, samp, crop, out_size, rep=3 if events_bins == 1 else 1)
     return dict(warp_image=r['f'], events_vg=ev, warp_img_self_res=isr)
 
