@@ -33,20 +33,13 @@ struct Plan {
   long blocks;      // tiles * splits * batch * batch2
 };
 
-static bool dma_view_ok(const GemmView& v) {
-  return v.vec_ok && v.in_dil <= 1 && v.R < (1L << 31) && v.Cc < (1L << 31) && (!v.conv || (v.H < 32768 && v.W < 32768)) &&
-         (v.conv || (v.ld % 8) == 0) && (v.Cc % 8) == 0 &&
-         (v.conv != 2 || ((v.KW * v.C) % 64 == 0 && v.KH == v.stride && v.KW == v.stride && v.pad == 0 && v.dil == 1 &&
-                          v.H == v.OH * v.stride && v.W == v.OW * v.stride));
-}
-
 // which problems the grouped kernels take, and on which tile: the largest tile that divides the output evenly (a 64x64 tile moves
 // 16 KB through L2 -> LDS per 0.5 MFLOP, 128x128 32 KB per 2.1 MFLOP: the k-loop is bound by that per-CU rate)
 static Plan classify(const GemmParams& p) {
   Plan pl{-1, 1, 0, 0, 0};
   if (p.dtype == CMDA_F32X3) {   // split-bf16 mode: the weight gradients the lean split kernel takes (its own eligibility test)
     const int b2 = p.batch2 > 0 ? p.batch2 : 1;
-    if (!(p.atomic && p.out_f32 && p.a_kstrided && p.b_kstrided && p.tile_hint == 0 && p.splits <= 0 && p.batch == 1 && b2 == 1 && p.M > 0 && p.N > 0 &&
+    if (!(p.atomic && p.out_f32 && p.a_kstrided && p.b_kstrided && !decode_hint(p.tile_hint).any && p.splits <= 0 && p.batch == 1 && b2 == 1 && p.M > 0 && p.N > 0 &&
           cmda_gemm_x3_lean_ok_(p)) || 2.0 * p.M * p.N * (double)p.K > 30e9)
       return pl;
     pl.bucket = 5 * 3;
@@ -55,7 +48,7 @@ static Plan classify(const GemmParams& p) {
     return pl;
   }
   const bool ok = p.dtype == CMDA_BF16 && p.atomic && p.out_f32 && p.a_kstrided && p.b_kstrided && p.A.conv != 1 && p.batch >= 1 &&
-                  p.M > 0 && p.N > 0 && p.K > 0 && dma_view_ok(p.A) && dma_view_ok(p.B) && p.tile_hint == 0 && p.splits <= 0 &&
+                  p.M > 0 && p.N > 0 && p.K > 0 && gemm_dma_view_ok(p.A, false) && gemm_dma_view_ok(p.B, false) && !decode_hint(p.tile_hint).any && p.splits <= 0 &&
                   !p.bias && !p.act && !p.res && !p.rowscale && p.c_patch_ow == 0;
   if (!ok) return pl;
   // a problem that fills the chip by itself (the decode head's weight gradients over 262144 rows: 0.14 - 1.2 TFLOP each) keeps
@@ -218,10 +211,10 @@ extern "C" int cmda_gemm_grouped(const cmda_gemm_params_t* params, int n, void* 
       if (!cnt) continue;
       const void* bptr = dblk + g.start[b] * 8;
       const int kind = b / 3, bc = b % 3;   // bc: operand class (0 fast plain, 1 general, 2 im2col B)
-      const int rc = kind == 0 ? cmda_gemm_grouped_t2_(dtab, bptr, (int)cnt, bc, stream)
-                   : kind == 1 ? cmda_gemm_grouped_t1_(dtab, bptr, (int)cnt, bc, stream)
-                   : kind == 2 ? cmda_gemm_grouped_t3_(dtab, bptr, (int)cnt, bc, stream)
-                   : kind == 3 ? cmda_gemm_grouped_t0_(dtab, bptr, (int)cnt, bc, stream)
+      const int rc = kind == 0 ? cmda_gemm_grouped_64x64_(dtab, bptr, (int)cnt, bc, stream)
+                   : kind == 1 ? cmda_gemm_grouped_128x64_(dtab, bptr, (int)cnt, bc, stream)
+                   : kind == 2 ? cmda_gemm_grouped_64x128_(dtab, bptr, (int)cnt, bc, stream)
+                   : kind == 3 ? cmda_gemm_grouped_128x128_(dtab, bptr, (int)cnt, bc, stream)
                    : kind == 4 ? cmda_gemm_wg_grouped_(dtab, bptr, (int)cnt, bc, stream)
                                : cmda_gemm_x3_lean_grouped_(dtab, bptr, (int)cnt, stream);
       if (rc != CMDA_OK) return rc;

@@ -24,10 +24,50 @@
 #include "common.h"
 #include "../../include/cmda_hip.h"
 
+// ---- host-side dispatch: everything that is a CHOICE about one cmda_gemm launch (gemm.hip plan_gemm makes it, the launchers below
+// take it; what stays with a launcher is its kernel's own knowledge: the DMA address-mode instance, DmaSrc::mode_ok) ----
+enum GemmFamily {   // kGemmNone: nothing to launch, GemmPlan.err is the return code (an empty problem, or one no kernel takes)
+  kGemmNone, kGemmPingPong /* gemm_pp.hip */, kGemmWgrad /* gemm_wg.hip */, kGemmGlds /* gemm_glds_kernel, gemm_t0..t3.hip */,
+  kGemmLean /* gemm_lean.hip */, kGemmReg /* gemm_kernel, gemm_reg_*.hip: bf16 and exact fp32 */, kGemmX3Reg /* gemm_x3.hip */,
+  kGemmX3Lean /* gemm_x3_lean.hip: 64x64 on eight waves; weight gradients: its launcher's own split count */
+};
+enum GemmTile { kTile128x128, kTile128x64, kTile64x64, kTile256x256 };   // (tile_hint bits 0-3 hold the value + 1)
+constexpr int kGemmTileBM[4] = {128, 128, 64, 256}, kGemmTileBN[4] = {128, 64, 64, 256};
+
+struct GemmHint {        // cmda_gemm_params_t.tile_hint, decoded (include/cmda_hip.h documents the layout; bit 8 is read by the device code)
+  bool any, valid, reg;  // != 0; 0, negative or positive with known bits only; negative: the register-staged kernel
+  int tile, stages;      // bits 0-3: 1..4 = GemmTile + 1, else the heuristics; bits 4-7: 0 = the four-stage rule, 4 = four stages, else two
+  bool glds256, ping_pong, general_addr, no_lean, x3_lean;   // bits 9, 10, 11, 13, 16
+};
+static inline GemmHint decode_hint(int h) {
+  constexpr int kKnown = 0xfff | (1 << 13) | (1 << 16);
+  const bool pos = h > 0;
+  return GemmHint{h != 0, !pos || !(h & ~kKnown), h < 0, pos ? (h & 15) : 0, pos ? ((h >> 4) & 15) : 0, pos && (h & 512), pos && (h & 1024),
+                  pos && (h & 2048), pos && (h & 8192), pos && (h & 65536)};
+}
+
+struct GemmPlan {
+  int err;             // CMDA_OK, or why nothing runs
+  GemmFamily family;
+  GemmTile tile;
+  int stages, waves;   // LDS stages (kGemmGlds / kGemmLean: 2 = throughput, 4 = latency configuration; others 0: the kernel's own), waves per workgroup
+  int splits;          // grid z = batch * batch2 * splits (kGemmX3Lean weight gradients: replaced by the launcher's own count)
+  bool general_addr;   // GemmHint.general_addr
+};
+
 namespace {
 
 typedef cmda_view_t GemmView;
 typedef cmda_gemm_params_t GemmParams;
+
+// LDS-DMA eligibility of one operand view: aligned 16-byte chunks, 32-bit tile arithmetic (reflection padding included).  Zero-inserted
+// inputs (in_dil > 1 -- transposed convolutions, data gradients of strided ones): only where the caller says so.
+static inline bool gemm_dma_view_ok(const GemmView& v, bool in_dil_ok) {
+  return v.vec_ok && (v.in_dil <= 1 || in_dil_ok) && v.R < (1L << 31) && v.Cc < (1L << 31) && (!v.conv || (v.H < 32768 && v.W < 32768)) &&
+         (v.conv || (v.ld % 8) == 0) && (v.Cc % 8) == 0 &&
+         (v.conv != 2 || ((v.KW * v.C) % 64 == 0 && v.KH == v.stride && v.KW == v.stride && v.pad == 0 && v.dil == 1 &&
+                          v.H == v.OH * v.stride && v.W == v.OW * v.stride));
+}
 
 static __device__ __forceinline__ int reflect_idx(int i, int n) {
   if (i < 0) i = -i;
@@ -1191,52 +1231,40 @@ __global__ __launch_bounds__(64 * NW, (GldsCfg<TM, TN, NW, NSV>::MIN_WAVES)) voi
 }
 
 template <int TM, int TN, int NW, int NSV, bool AKS, bool BKS, bool ACONV, bool BCONV>
-int launch_glds_mode(const GemmParams& p, const dim3& grid, void* stream) {
+int launch_glds_mode(const GemmParams& p, bool general_addr, const dim3& grid, void* stream) {
   constexpr int BM = 16 * TM * (NW / 2), BN = 32 * TN;
   const dim3 blk(64 * NW);
   typedef DmaSrc<AKS, BM, ACONV, NW, 0, 64, DmaMode<AKS, ACONV, true>::value> FA;
   typedef DmaSrc<BKS, BN, BCONV, NW, 0, 64, DmaMode<BKS, BCONV, true>::value> FB;
-  const bool fast = FA::mode_ok(p.A, FA::MODE) && FB::mode_ok(p.B, FB::MODE) && (FA::MODE != 0 || FB::MODE != 0) &&
-                    !(p.tile_hint > 0 && (p.tile_hint & 2048));   // (tile_hint bit 11: force the general address path, tuning A/B)
+  const bool fast = FA::mode_ok(p.A, FA::MODE) && FB::mode_ok(p.B, FB::MODE) && (FA::MODE != 0 || FB::MODE != 0) && !general_addr;
   if (fast) CMDA_LAUNCH((gemm_glds_kernel<TM, TN, AKS, BKS, ACONV, BCONV, NW, NSV, true>), grid, blk, 0, stream, p);
   else CMDA_LAUNCH((gemm_glds_kernel<TM, TN, AKS, BKS, ACONV, BCONV, NW, NSV, false>), grid, blk, 0, stream, p);
   CMDA_CHECK_LAUNCH();
 }
 
 template <int TM, int TN, int NW, int NSV>
-int launch_glds_ns(const GemmParams& p, const dim3& grid, void* stream) {
+int launch_glds_ns(const GemmParams& p, bool general_addr, const dim3& grid, void* stream) {
   const bool aks = p.a_kstrided != 0, bks = p.b_kstrided != 0, ac = p.A.conv == 1, bc = p.B.conv == 1;  // (2 = patch view: plain fills)
-  if (!aks && !bks && !ac && !bc) return launch_glds_mode<TM, TN, NW, NSV, false, false, false, false>(p, grid, stream);
-  if (!aks && bks && !ac && !bc) return launch_glds_mode<TM, TN, NW, NSV, false, true, false, false>(p, grid, stream);
-  if (aks && bks && !ac && !bc) return launch_glds_mode<TM, TN, NW, NSV, true, true, false, false>(p, grid, stream);
-  if (aks && !bks && !ac && !bc) return launch_glds_mode<TM, TN, NW, NSV, true, false, false, false>(p, grid, stream);
-  if (!aks && !bks && ac && !bc) return launch_glds_mode<TM, TN, NW, NSV, false, false, true, false>(p, grid, stream);
-  if (aks && bks && !ac && bc) return launch_glds_mode<TM, TN, NW, NSV, true, true, false, true>(p, grid, stream);
+  if (!aks && !bks && !ac && !bc) return launch_glds_mode<TM, TN, NW, NSV, false, false, false, false>(p, general_addr, grid, stream);
+  if (!aks && bks && !ac && !bc) return launch_glds_mode<TM, TN, NW, NSV, false, true, false, false>(p, general_addr, grid, stream);
+  if (aks && bks && !ac && !bc) return launch_glds_mode<TM, TN, NW, NSV, true, true, false, false>(p, general_addr, grid, stream);
+  if (aks && !bks && !ac && !bc) return launch_glds_mode<TM, TN, NW, NSV, true, false, false, false>(p, general_addr, grid, stream);
+  if (!aks && !bks && ac && !bc) return launch_glds_mode<TM, TN, NW, NSV, false, false, true, false>(p, general_addr, grid, stream);
+  if (aks && bks && !ac && bc) return launch_glds_mode<TM, TN, NW, NSV, true, true, false, true>(p, general_addr, grid, stream);
   return CMDA_ERR_UNSUPPORTED;
 }
 
 template <int TM, int TN, int NW = 4>
-int launch_glds(const GemmParams& p, void* stream) {
+int launch_glds(const GemmParams& p, const GemmPlan& plan, void* stream) {
   constexpr int BM = 16 * TM * (NW / 2), BN = 32 * TN;
   const long tiles = (long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
   const long zz = (long)p.batch * p.batch2 * p.splits;
   if (tiles > 0x7fffffffL || zz > 65535) return CMDA_ERR_SHAPE;
   dim3 grid((unsigned)tiles, 1, (unsigned)zz);
-  if constexpr (NW == 4) {
-    // latency configuration: the whole grid is resident at once even at 4 stages (64x64: 64 KiB -> 2 blocks per CU; the wider
-    // tiles: 96 / 128 KiB -> 1 block per CU) and every block runs >= 12 k-tiles (K >= 768)
-    constexpr long kStage = (long)(BM + BN) * 128;
-    const long resident = 256L * (4 * kStage <= 65536 ? 2 : 1);
-    const long nkt = ((long)p.K + 63) / 64 / (p.splits > 0 ? p.splits : 1);
-    const int force = p.tile_hint > 0 ? ((p.tile_hint >> 4) & 15) : 0;   // tuning sweeps (tools/gemm_sweep.py): stages in bits 4.. of the hint
-    if (force) return force == 4 ? launch_glds_ns<TM, TN, NW, 4>(p, grid, stream) : launch_glds_ns<TM, TN, NW, 0>(p, grid, stream);
-    // (deeper than 4 -- 8 x 16 KiB on the 64x64 tile, 6 x 24 KiB on 128x64, one block per CU -- measured slower on every shape
-    // of the step: profiles/r02_gemm_sweep.txt)
-    const int min_nkt = (p.tile_hint > 0 && (p.tile_hint >> 12)) ? (p.tile_hint >> 12) : 12;   // (bits 12..: tuning sweeps; in the step 12 k-tiles measured
-                                                                                                // 77.5-78.1 ms against 78.0-78.2 at 3 and 78.2-79.2 at 40)
-    if (tiles * zz <= resident && nkt >= min_nkt) return launch_glds_ns<TM, TN, NW, 4>(p, grid, stream);
+  if constexpr (NW == 4) {   // (the latency configuration: four-wave tiles only)
+    if (plan.stages == 4) return launch_glds_ns<TM, TN, NW, 4>(p, plan.general_addr, grid, stream);
   }
-  return launch_glds_ns<TM, TN, NW, 0>(p, grid, stream);
+  return launch_glds_ns<TM, TN, NW, 0>(p, plan.general_addr, grid, stream);
 }
 
 // grouped launch of the weight-gradient operand modes (A and B K-strided; B plain / patch view, or an im2col view)
@@ -1271,24 +1299,25 @@ int launch_tile(const GemmParams& p, void* stream) {
 }  // namespace
 
 // cross-unit entry points (C++ linkage, not part of the C ABI)
-int cmda_gemm_glds_t0_(const cmda_gemm_params_t& p, void* stream);        // gemm_t0.hip: 128x128 tile
-int cmda_gemm_glds_t1_(const cmda_gemm_params_t& p, void* stream);        // gemm_t1.hip: 128x64 tile
-int cmda_gemm_glds_t2_(const cmda_gemm_params_t& p, void* stream);        // gemm_t2.hip: 64x64 tile
-int cmda_gemm_glds_t3_(const cmda_gemm_params_t& p, void* stream);        // gemm_t3.hip: 256x256 tile, 8 waves
-bool cmda_gemm_lean_ok_(const cmda_gemm_params_t& p, int tile);           // gemm_lean.hip: lean plain-operand instance (64x64 / 128x64)
-int cmda_gemm_lean_(const cmda_gemm_params_t& p, int tile, int four_stage, void* stream);
-int cmda_gemm_grouped_t2_(const cmda_gemm_params_t* tab, const void* blk, int nblocks, int bconv, void* stream);  // gemm_g2.hip: 64x64
-int cmda_gemm_grouped_t0_(const cmda_gemm_params_t* tab, const void* blk, int nblocks, int bconv, void* stream);  // gemm_g0.hip: 128x128
-int cmda_gemm_grouped_t1_(const cmda_gemm_params_t* tab, const void* blk, int nblocks, int bconv, void* stream);  // gemm_g1.hip: 128x64
-int cmda_gemm_grouped_t3_(const cmda_gemm_params_t* tab, const void* blk, int nblocks, int bconv, void* stream);  // gemm_g3.hip: 64x128
+// (the launchers run what gemm.hip's plan_gemm decided: `plan`; p.splits is the plan's)
+int cmda_gemm_glds_t0_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream);   // gemm_t0.hip: 128x128 tile
+int cmda_gemm_glds_t1_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream);   // gemm_t1.hip: 128x64 tile
+int cmda_gemm_glds_t2_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream);   // gemm_t2.hip: 64x64 tile
+int cmda_gemm_glds_t3_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream);   // gemm_t3.hip: 256x256 tile, 8 waves
+bool cmda_gemm_lean_ok_(const cmda_gemm_params_t& p);                     // gemm_lean.hip: lean plain-operand instance (64x64 / 128x64)
+int cmda_gemm_lean_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream);
+int cmda_gemm_grouped_64x64_(const cmda_gemm_params_t* tab, const void* blk, int nblocks, int bconv, void* stream);  // gemm_g2.hip: 64x64
+int cmda_gemm_grouped_128x128_(const cmda_gemm_params_t* tab, const void* blk, int nblocks, int bconv, void* stream);  // gemm_g0.hip: 128x128
+int cmda_gemm_grouped_128x64_(const cmda_gemm_params_t* tab, const void* blk, int nblocks, int bconv, void* stream);  // gemm_g1.hip: 128x64
+int cmda_gemm_grouped_64x128_(const cmda_gemm_params_t* tab, const void* blk, int nblocks, int bconv, void* stream);  // gemm_g3.hip: 64x128
 int cmda_gemm_wg_grouped_(const cmda_gemm_params_t* tab, const void* blk, int nblocks, int bconv, void* stream);  // gemm_wg.hip, grouped
-int cmda_gemm_wg_(const cmda_gemm_params_t& p, void* stream);             // gemm_wg.hip: 256x256 weight-gradient kernel (32x32x16 MFMA, atomics)
-int cmda_gemm_pp_(const cmda_gemm_params_t& p, void* stream);             // gemm_pp.hip: 256x256 ping-pong kernel (32x32x16 MFMA)
-int cmda_gemm_reg_(const cmda_gemm_params_t& p, int tile, void* stream);  // gemm_reg.hip: register-staged kernels, dispatch
-int cmda_gemm_x3_(const cmda_gemm_params_t& p, int tile, void* stream);
+int cmda_gemm_wg_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream);   // gemm_wg.hip: 256x256 weight-gradient kernel (32x32x16 MFMA, atomics)
+int cmda_gemm_pp_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream);   // gemm_pp.hip: 256x256 ping-pong kernel (32x32x16 MFMA)
+int cmda_gemm_reg_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream);  // gemm_reg.hip: register-staged kernels (bf16, fp32)
+int cmda_gemm_x3_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream);   // gemm_x3.hip: fp32 storage, split-bf16 (bf16 x 3) MFMA
 bool cmda_gemm_x3_lean_ok_(const cmda_gemm_params_t& p);                   // gemm_x3_lean.hip: LDS-DMA split-bf16 kernel, plain operands
-int cmda_gemm_x3_lean_(const cmda_gemm_params_t& p, void* stream);
-int cmda_gemm_x3_lean_grouped_(const cmda_gemm_params_t* tab, const void* blk, int nblocks, void* stream);   // grouped weight-gradient form   // gemm_x3.hip: fp32 storage, split-bf16 (bf16 x 3) MFMA
+int cmda_gemm_x3_lean_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream);
+int cmda_gemm_x3_lean_grouped_(const cmda_gemm_params_t* tab, const void* blk, int nblocks, void* stream);   // grouped weight-gradient form
 // gemm_reg_{f32,bf16}_t{0,1,2}.hip: one (dtype, tile) each -- these are the slow units to compile (~50 s apiece)
 int cmda_gemm_reg_f32_t0_(const cmda_gemm_params_t& p, void* stream);
 int cmda_gemm_reg_f32_t1_(const cmda_gemm_params_t& p, void* stream);

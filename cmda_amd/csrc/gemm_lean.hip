@@ -9,7 +9,7 @@
 // and the epilogue starts its bias / residual loads only when the accumulators are final.  Here the host digests the problem into a
 // 128-byte block that is read in ONE round trip, the prologue is straight-line pointer arithmetic, and the epilogue's bias and
 // residual loads are issued before the k-loop's last barrier.
-// Eligibility (host, cmda_gemm -> launch_dtype): bf16, plain operands (no im2col / patch view), A K-contiguous, B K-contiguous or
+// Eligibility (host, cmda_gemm -> plan_gemm): bf16, plain operands (no im2col / patch view), A K-contiguous, B K-contiguous or
 // K-strided, K % 64 == 0, no batch, no split-K, no atomic / patch-store / column-sum output; tiles 64 x 64 and 128 x 64.
 #include "gemm_kernels.h"
 
@@ -330,17 +330,14 @@ int launch_lean(const GemmParams& p, void* stream) {
   q.alpha = p.alpha; q.beta = p.beta;
   const dim3 grid((unsigned)tiles), blk(64 * NW);
   if (p.A.conv == 2) {
-    if constexpr (NSV == 0 && NW == 4) return CMDA_ERR_UNSUPPORTED;   // (the four-wave 2-stage tuning variants: plain operands only)
-    else {
-      const GemmView& v = p.A;
-      q.p_img = (long)v.H * v.W * v.C;
-      q.p_ohw = v.OH * v.OW; q.p_ow = v.OW;
-      q.p_row = v.stride * v.W * v.C; q.p_col = v.stride * v.C;
-      q.p_seg = v.KW * v.C / 64;
-      q.p_jump = (v.W - v.KW) * v.C * 2;
-      CMDA_LAUNCH((gemm_lean_kernel<TM, TN, false, NSV, NW, true>), grid, blk, 0, stream, q);
-      CMDA_CHECK_LAUNCH();
-    }
+    const GemmView& v = p.A;
+    q.p_img = (long)v.H * v.W * v.C;
+    q.p_ohw = v.OH * v.OW; q.p_ow = v.OW;
+    q.p_row = v.stride * v.W * v.C; q.p_col = v.stride * v.C;
+    q.p_seg = v.KW * v.C / 64;
+    q.p_jump = (v.W - v.KW) * v.C * 2;
+    CMDA_LAUNCH((gemm_lean_kernel<TM, TN, false, NSV, NW, true>), grid, blk, 0, stream, q);
+    CMDA_CHECK_LAUNCH();
   }
   if (p.c_patch_ow > 0) {
     q.flags |= 8;
@@ -353,31 +350,26 @@ int launch_lean(const GemmParams& p, void* stream) {
 
 }  // namespace
 
-// HOST: does the lean kernel take this problem?  (tile: launch_dtype's choice, 1 = 128 x 64, 2 = 64 x 64)
-bool cmda_gemm_lean_ok_(const cmda_gemm_params_t& p, int tile) {
+// HOST: does the lean kernel take this problem?  (on the 128 x 64 and 64 x 64 tiles: gemm.hip plan_gemm)
+bool cmda_gemm_lean_ok_(const cmda_gemm_params_t& p) {
   auto plain = [](const GemmView& v) { return v.conv == 0 && v.vec_ok && (v.ld % 8) == 0 && v.R < (1L << 31) && v.Cc < (1L << 31); };
   // patch view of a kernel == stride convolution as A (K-contiguous B): KW * C a multiple of the k-tile, 32-bit row arithmetic
   auto patch = [&](const GemmView& v) {
     return v.conv == 2 && v.vec_ok && !p.b_kstrided && v.KH == v.stride && v.KW == v.stride && v.pad == 0 && v.dil == 1 && v.in_dil <= 1 &&
            v.H == v.OH * v.stride && v.W == v.OW * v.stride && ((long)v.KW * v.C) % 64 == 0 && v.R < (1L << 31) &&
-           (long)v.stride * v.W * v.C * 2 < (1L << 31) && (long)v.OH * v.OW < (1L << 31) && p.K == (long)v.KH * v.KW * v.C &&
-           !(p.tile_hint > 0 && (p.tile_hint & 16384));
+           (long)v.stride * v.W * v.C * 2 < (1L << 31) && (long)v.OH * v.OW < (1L << 31) && p.K == (long)v.KH * v.KW * v.C;
   };
-  return (tile == 1 || tile == 2) && p.dtype == CMDA_BF16 && !p.a_kstrided && (plain(p.A) || patch(p.A)) && plain(p.B) && (p.K % 64) == 0 && p.K >= 64 &&
+  return p.dtype == CMDA_BF16 && !p.a_kstrided && (plain(p.A) || patch(p.A)) && plain(p.B) && (p.K % 64) == 0 && p.K >= 64 &&
          p.batch == 1 && p.batch2 <= 1 && p.splits <= 1 && !p.atomic && !p.colsum && p.c_perm_ci == 0 &&
          (p.c_patch_ow == 0 || (plain(p.A) && !p.res && (long)p.M * p.N < (1L << 31) && p.c_patch_kwci > 0)) &&
-         (!p.b_kstrided || 64L * p.B.ld * 2 < (1L << 31)) && !(p.tile_hint > 0 && (p.tile_hint & 8192));   // (tile_hint bit 13: general kernel, tuning A/B)
+         (!p.b_kstrided || 64L * p.B.ld * 2 < (1L << 31));
 }
 
-int cmda_gemm_lean_(const cmda_gemm_params_t& p, int tile, int four_stage, void* stream) {
-  // The 2-stage configurations run on EIGHT waves (16 x 32 / 32 x 32 of the tile per wave): a lone workgroup's k-tile is bound by how
-  // fast its waves can issue LDS-DMA pieces (0.3 us per 16 KiB with four waves), and twice the waves issue half the pieces each --
-  // 2048 x 320 x 320 5.05 -> 4.31 us, 8192 x 1280 x 320 18.6 -> 16.6, the step 60.2 -> 59.0 ms (gpurun r04u; the 4-stage
-  // configurations measured the same on 4 and 8 waves and stay on 4).  tile_hint bit 14: four waves (tuning A/B).
-  const bool w4 = p.tile_hint > 0 && (p.tile_hint & 16384);
-  if (!four_stage && !w4) return tile == 1 ? launch_lean<2, 2, 0, 8>(p, stream) : launch_lean<1, 2, 0, 8>(p, stream);
-  if (four_stage) return tile == 1 ? launch_lean<4, 2, 4>(p, stream) : launch_lean<2, 2, 4>(p, stream);
-  return tile == 1 ? launch_lean<4, 2>(p, stream) : launch_lean<2, 2>(p, stream);
+// the plan's two configurations: 2 stages on eight waves, 4 stages on four (gemm.hip plan_gemm has the measurements)
+int cmda_gemm_lean_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream) {
+  const bool wide = plan.tile == kTile128x64;
+  if (plan.stages == 4) return wide ? launch_lean<4, 2, 4>(p, stream) : launch_lean<2, 2, 4>(p, stream);
+  return wide ? launch_lean<2, 2, 0, 8>(p, stream) : launch_lean<1, 2, 0, 8>(p, stream);
 }
 
 #ifdef CMDA_LEAN_TIMING

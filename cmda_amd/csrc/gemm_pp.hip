@@ -350,14 +350,14 @@ extern "C" int cmda_debug_pp_stamps(unsigned long long* host_out) {
 #endif
 
 // cross-unit entry (gemm.hip decides eligibility): returns CMDA_ERR_UNSUPPORTED for operand modes this kernel does not take
-int cmda_gemm_pp_(const cmda_gemm_params_t& p, void* stream) {
+int cmda_gemm_pp_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream) {
   const long tiles = (long)((p.M + PP_BM - 1) / PP_BM) * ((p.N + PP_BN - 1) / PP_BN);
   const long zz = (long)p.batch * p.batch2;
   if (tiles > 0x7fffffffL || zz > 65535) return CMDA_ERR_SHAPE;
   const dim3 grid((unsigned)tiles, 1, (unsigned)zz), blk(512);
   const bool bks = p.b_kstrided != 0, ac = p.A.conv == 1;
   if (p.a_kstrided || p.B.conv == 1) return CMDA_ERR_UNSUPPORTED;
-  const bool nofast = p.tile_hint > 0 && (p.tile_hint & 2048);
+  const bool nofast = plan.general_addr;
   typedef DmaSrc<false, PP_BM, false, PP_NW, 1, 64, 1> FA;
   typedef DmaSrc<false, PP_BM, true, PP_NW, 1, 64, 2> FAC;
   typedef DmaSrc<false, PP_BN, false, PP_NW, 1, 64, 1> FB;

@@ -1,5 +1,5 @@
 // gemm_t0.hip -- the 128x128 instantiations of the LDS-DMA GEMM kernel (own translation unit: the six operand-mode
-// variants of a tile compile in parallel with the other tiles).  Templates: gemm_kernels.h; chosen by launch_dtype in gemm.hip.
+// variants of a tile compile in parallel with the other tiles).  Templates: gemm_kernels.h; chosen by plan_gemm in gemm.hip.
 #include "gemm_kernels.h"
 
-int cmda_gemm_glds_t0_(const cmda_gemm_params_t& p, void* stream) { return launch_glds<4, 4>(p, stream); }
+int cmda_gemm_glds_t0_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream) { return launch_glds<4, 4>(p, plan, stream); }

@@ -209,23 +209,19 @@ int cmda_gemm_wg_grouped_(const cmda_gemm_params_t* tab, const void* blk, int nb
 }
 
 // cross-unit entry (gemm.hip decides eligibility and the split count)
-int cmda_gemm_wg_(const cmda_gemm_params_t& p, void* stream) {
+int cmda_gemm_wg_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream) {
   const long tiles = (long)((p.M + WG_T - 1) / WG_T) * ((p.N + WG_T - 1) / WG_T);
   const long zz = (long)p.batch * p.batch2 * p.splits;
   if (tiles > 0x7fffffffL || zz > 65535) return CMDA_ERR_SHAPE;
   const dim3 grid((unsigned)tiles, 1, (unsigned)zz), blk(512);
-  const bool nofast = p.tile_hint > 0 && (p.tile_hint & 2048);
+  const bool nofast = plan.general_addr;
   if (p.B.conv == 1) {
     // FAST: dY in the running-pointer mode, the im2col operand in the row-fast mode (stride-1 "same" convolution, output rows of
-    // whole k-tiles: the head's 3 x 3 bottleneck).  tile_hint bit 12 (tuning A/B): the plain operands' four half-depth stages for the
-    // im2col view too -- measured SLOWER (1907 against 1690 us on the general path's two full-depth stages, gpurun r04f)
+    // whole k-tiles: the head's 3 x 3 bottleneck).  (The plain operands' four half-depth stages for the im2col view too measured
+    // SLOWER: 1907 against 1690 us on the general path's two full-depth stages)
     typedef DmaSrc<true, WG_T, false, WG_NW, 0, 64, 1> FA;
     typedef DmaSrc<true, WG_T, true, WG_NW, 0, 64, 3> FB;
-    typedef DmaSrc<true, WG_T, false, WG_NW, 0, 32, 1> FA32;
-    typedef DmaSrc<true, WG_T, true, WG_NW, 0, 32, 3> FB32;
-    if (!nofast && FA32::mode_ok(p.A, 1) && FB32::mode_ok(p.B, 3) && (p.tile_hint > 0 && (p.tile_hint & 4096)))
-      CMDA_LAUNCH((gemm_wg_kernel<true, 32, 4, true>), grid, blk, 0, stream, p);
-    else if (!nofast && FA::mode_ok(p.A, 1) && FB::mode_ok(p.B, 3)) CMDA_LAUNCH((gemm_wg_kernel<true, 64, 2, true>), grid, blk, 0, stream, p);
+    if (!nofast && FA::mode_ok(p.A, 1) && FB::mode_ok(p.B, 3)) CMDA_LAUNCH((gemm_wg_kernel<true, 64, 2, true>), grid, blk, 0, stream, p);
     else CMDA_LAUNCH((gemm_wg_kernel<true, 64, 2, false>), grid, blk, 0, stream, p);
   } else {
     typedef DmaSrc<true, WG_T, false, WG_NW, 0, 32, 1> FA;

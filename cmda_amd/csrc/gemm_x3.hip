@@ -5,7 +5,7 @@
 // Replaces, for cmda_gemm_params_t.dtype == CMDA_F32X3, the exact-fp32 kernel (v_mfma_f32_16x16x4_f32 at 1/16 of the bf16 MFMA
 // rate, gemm_kernels.h gemm_kernel<float>): 3/16 of its matrix-pipe time for the same operand bytes -- the mode that meets the
 // north star's 1e-3 logit tolerance without paying the fp32 matrix rate.  Same operand views, same fused epilogue,
-// same tile / split-K heuristics (gemm.hip launch_dtype<float>); reference call sites as gemm_kernels.h.
+// same tile / split-K heuristics (gemm.hip plan_gemm); reference call sites as gemm_kernels.h.
 #include "gemm_kernels.h"
 
 namespace {
@@ -225,7 +225,6 @@ int launch_x3(const GemmParams& p, void* stream) {
 
 }  // namespace
 
-int cmda_gemm_x3_(const cmda_gemm_params_t& p, int tile, void* stream) {
-  const int t = (tile == 3) ? 0 : (tile == 4 ? 2 : tile);
-  return t == 0 ? launch_x3<4, 4>(p, stream) : t == 1 ? launch_x3<4, 2>(p, stream) : launch_x3<2, 2>(p, stream);
+int cmda_gemm_x3_(const cmda_gemm_params_t& p, const GemmPlan& plan, void* stream) {
+  return plan.tile == kTile128x128 ? launch_x3<4, 4>(p, stream) : plan.tile == kTile128x64 ? launch_x3<4, 2>(p, stream) : launch_x3<2, 2>(p, stream);
 }

@@ -559,7 +559,7 @@ bool cmda_gemm_x3_lean_ok_(const cmda_gemm_params_t& p) {
   };
   if (!(p.dtype == CMDA_F32X3 && (plain(p.A) || patch_a(p.A)) && (plain(p.B) || patch_b(p.B)) && (p.K % 32) == 0 && p.K >= 32 && p.batch >= 1 && nb <= 65535 &&
         bs_ok(p.A) && bs_ok(p.B) && (p.c_batch_stride % 4) == 0 && (p.c_batch2_stride % 4) == 0 && (nb == 1 || !p.colsum) &&
-        p.c_perm_ci == 0 && p.out_f32 && (p.N % 4) == 0 && !(p.tile_hint > 0 && (p.tile_hint & 8192))))   // (bit 13: general kernel, tuning A/B)
+        p.c_perm_ci == 0 && p.out_f32 && (p.N % 4) == 0))
     return false;
   if (p.a_kstrided)   // weight-gradient form: dW (+)= dy^T x with fp32 atomics, any split count (the kernel chooses its own)
     return p.b_kstrided && p.atomic && (p.M % 4) == 0 && !p.bias && !p.res && !p.rowscale && p.act == 0 && p.beta == 0.f && p.c_patch_ow == 0 &&
@@ -572,7 +572,7 @@ bool cmda_gemm_x3_lean_ok_(const cmda_gemm_params_t& p) {
   return p.splits <= 1;
 }
 
-int cmda_gemm_x3_lean_(const cmda_gemm_params_t& p, void* stream) { return launch_x3_lean(p, stream); }
+int cmda_gemm_x3_lean_(const cmda_gemm_params_t& p, const GemmPlan&, void* stream) { return launch_x3_lean(p, stream); }
 
 // grouped weight-gradient launch (gemm_grouped.hip plans the splits and the block map; tab / blk are DEVICE pointers)
 int cmda_gemm_x3_lean_grouped_(const cmda_gemm_params_t* tab, const void* blk, int nblocks, void* stream) {

@@ -82,10 +82,11 @@ typedef struct cmda_gemm_params_t {
    * column buffer.  Off when c_patch_ow == 0; ldc / batch strides / residual are ignored in this mode. */
   int32_t c_patch_ow, c_patch_kh, c_patch_kwci;
   /* 0: the library's tile heuristics; -1: register-staged kernel instead of the LDS-DMA one.  > 0 (tuning sweeps, tests of the rarely
-   * chosen kernels): low 4 bits 1..4 force tile 128x128 / 128x64 / 64x64 / 256x256; bits 4-7 LDS stages (4 = four);
-   * bit 8 no tile-group walk; bit 9 gemm_glds_kernel instead of the ping-pong / weight-gradient 256x256 kernels; bit 10 ping-pong
-   * kernel; bit 11 general DMA address path; bit 12 (32, 4) weight-gradient configuration; bit 13 general kernel instead of the lean
-   * one; bit 14 lean kernel on four waves. */
+   * chosen kernels): bits 0-3 = 1..4 force tile 128x128 / 128x64 / 64x64 / 256x256; bits 4-7 LDS stages of the four-wave LDS-DMA
+   * kernels (4 = four, any other non-zero value = two); bit 8 no tile-group walk; bit 9 gemm_glds_kernel instead of the ping-pong /
+   * weight-gradient 256x256 kernels; bit 10 ping-pong kernel whatever the contraction depth; bit 11 general DMA address path; bit 13
+   * general kernel instead of the lean one (bf16 and split-bf16); bit 16 (split-bf16) the lean kernel whatever the tile choice.
+   * Every other bit of a positive hint is refused (CMDA_ERR_UNSUPPORTED). */
   int32_t tile_hint;
   /* atomic stores only, c_perm_ci > 0: GEMM column n = cell * c_perm_ci + ci (cell = kh*KW + kw, the im2col column order) is
    * stored at column ci * c_perm_cells + cell -- a convolution's weight gradient accumulated straight into the parameter's
