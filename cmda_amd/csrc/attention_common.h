@@ -94,21 +94,6 @@ static __device__ __forceinline__ void softmax_keys(int Nk, float scale, int g, 
     for (int r = 0; r < 4; ++r) p[t][r] *= inv;
 }
 
-// scores^T of 16 queries against all key tiles, then the softmax over keys: p[t][r] = P^T[key 16t + 4g + r][query l15]
-template <int NT = kNT>
-static __device__ __forceinline__ void scores_softmax(const bf16_t* sK, const u16x8 (&qf)[2], int nt, int Nk, float scale,
-                                                      int g, int l15, f32x4 (&p)[NT], float* lse_out = nullptr) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    p[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (t < nt) {
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) p[t] = mfma_bf16_16x16x32(frag_rows(sK, 16 * t, kk, g, l15), qf[kk], p[t]);
-    }
-  }
-  softmax_keys<NT>(Nk, scale, g, p, lse_out);
-}
-
 // FULL-KEY form (every one of the 16 * NT keys is live, scale > 0): no key mask, no tile guards, and the scale folded into the exponent.
 // The max is taken over the RAW scores (scale > 0 keeps the arg-max), e = exp2(s c - m c) with c = scale log2(e) is ONE fma and
 // one v_exp_f32 per score, and the probabilities are left UNNORMALISED in p: the callers apply the returned 1 / l to their 16
@@ -133,19 +118,6 @@ static __device__ __forceinline__ float exp_keys_full(float scale, f32x4 (&p)[NT
   l = col_sum(l);
   if (lse_out) *lse_out = m * scale + __logf(l);
   return 1.f / l;
-}
-
-// scores^T of 16 queries against all NT key tiles, then exp_keys_full: p[t][r] = l * P^T[key 16t + 4g + r][query l15]; returns 1 / l
-template <int NT = kNT>
-static __device__ __forceinline__ float scores_exp_full(const bf16_t* sK, const u16x8 (&qf)[2], float scale, int g, int l15,
-                                                        f32x4 (&p)[NT], float* lse_out = nullptr) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    p[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) p[t] = mfma_bf16_16x16x32(frag_rows(sK, 16 * t, kk, g, l15), qf[kk], p[t]);
-  }
-  return exp_keys_full<NT>(scale, p, lse_out);
 }
 
 static __device__ __forceinline__ u16x8 pack_pair(const f32x4& a, const f32x4& b) {
