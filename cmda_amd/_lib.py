@@ -1,5 +1,5 @@
 """ctypes binding of libcmda_hip.so (the C ABI declared in include/cmda_hip.h and its extensions include/cmda_hip_ext.h,
-include/cmda_hip_ext2.h, include/cmda_hip_ext3.h, include/cmda_hip_ext4.h and include/cmda_hip_ext5.h).
+include/cmda_hip_ext2.h, include/cmda_hip_ext3.h, include/cmda_hip_ext4.h, include/cmda_hip_ext5.h and include/cmda_hip_ext6.h).
 
 The product path has exactly one backend: the gfx950 kernel library built in-tree by
 ``__graft_entry__.build()`` / ``make hip``.  If it is missing, or a tensor is not on the GPU,
@@ -25,6 +25,7 @@ ABI_EXT2_VERSION = 1
 ABI_EXT3_VERSION = 1
 ABI_EXT4_VERSION = 1
 ABI_EXT5_VERSION = 1
+ABI_EXT6_VERSION = 1
 
 
 class View(ctypes.Structure):
@@ -102,6 +103,12 @@ def _declare(lib):
     lib.cmdax5_voxel_ordered_ws_bytes.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.cmdax5_events_norm_ws_bytes.restype = ctypes.c_int64
     lib.cmdax5_events_norm_ws_bytes.argtypes = [ctypes.c_int, ctypes.c_int64]
+    # the sixth table (include/cmda_hip_ext6.h): the split train type's per-stream targets
+    if not hasattr(lib, 'cmdax6_abi_version'):
+        raise CmdaError('the kernel library lacks the sixth ABI table (cmdax6_*): rebuild it')
+    lib.cmdax6_abi_version.restype = ctypes.c_int
+    if lib.cmdax6_abi_version() != ABI_EXT6_VERSION:
+        raise CmdaError('libcmda_hip.so sixth ABI table (cmdax6_*) version mismatch')
     return lib
 
 

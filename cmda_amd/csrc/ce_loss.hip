@@ -17,6 +17,7 @@
 // Backward is a deterministic gather over the 1/4-resolution grid (no atomics), one thread per (pixel, class).
 #include <cstdlib>
 #include "bilinear.h"
+#include "../../include/cmda_hip_ext6.h"
 
 namespace {
 constexpr int kMaxClasses = 32;
@@ -488,6 +489,83 @@ __global__ void pseudo_weight_kernel(const int* __restrict__ count, float* __res
   }
 }
 
+// The split train type's targets ('cs2dz_image+raw-isr_split', dacs.py:628-651, :759-763), launch A: pseudo_label_kernel over TWO logit
+// maps with the ClassMix of both pseudo-labels against the source label folded in.  The maps go through the one LDS patch one after the
+// other (stage_patch / tile_scores / the soft-max expression of pseudo_label_kernel: the same bits per map); the membership of the
+// source label in the sample's drawn classes is evaluated once per pixel and kept in registers for the second map.
+constexpr int kRowsPerThread = kTH / (256 / kTW);
+__global__ __launch_bounds__(256) void split_targets_kernel(const float* __restrict__ logits0, const float* __restrict__ logits1,
+                                                             const long long* __restrict__ src_label, const long long* __restrict__ classes,
+                                                             long long* __restrict__ pseudo, long long* __restrict__ mixed,
+                                                             int* __restrict__ count, int B, int h, int w, int H, int W, int nc, int K,
+                                                             float thr) {
+  __shared__ int red[2][4];
+  __shared__ float patch[kPatchFloats];
+  const float sh = (float)h / (float)H, sw = (float)w / (float)W;
+  const long total = (long)B * H * W;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  long long lab[kRowsPerThread];
+  bool src[kRowsPerThread];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const float* lg = s == 0 ? logits0 : logits1;
+    if (s) __syncthreads();   // every read of the first map's patch is done
+    const ScoreTile t = stage_patch(lg, patch, h, w, H, W, nc, sh, sw);
+    int cnt = 0;
+    const int X = t.X0 + (threadIdx.x & (kTW - 1));
+#pragma unroll
+    for (int j = 0; j < kRowsPerThread; ++j) {
+      const int Y = t.Y0 + (threadIdx.x / kTW) + j * (256 / kTW);
+      if (X >= W || Y >= H) continue;
+      const long i = ((long)t.b * H + Y) * W + X;
+      if (s == 0) {
+        lab[j] = src_label[i];
+        int msk = 0;
+        for (int k = 0; k < K; ++k) msk += (classes[(long)t.b * K + k] == lab[j]) ? 1 : 0;
+        src[j] = msk != 0;
+      }
+      const BilinTap ty = bilin_tap(Y, h, H, sh), tx = bilin_tap(X, w, W, sw);
+      float sc[kMaxClasses];
+      tile_scores<kMaxClasses>(t, lg, patch, h, w, nc, ty, tx, sc);
+      float mx = -INFINITY;
+      int am = 0;
+#pragma unroll
+      for (int c = 0; c < kMaxClasses; ++c)
+        if (c < nc && sc[c] > mx) { mx = sc[c]; am = c; }
+      float se = 0.f;
+#pragma unroll
+      for (int c = 0; c < kMaxClasses; ++c)
+        if (c < nc) se += __expf(sc[c] - mx);
+      const float prob = 1.f / se;
+      pseudo[s * total + i] = am;
+      mixed[s * total + i] = src[j] ? lab[j] : (long long)am;
+      cnt += prob >= thr ? 1 : 0;
+    }
+    const float cf = wave_sum((float)cnt);
+    if (lane == 0) red[s][wid] = (int)cf;
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) atomicAdd(count + threadIdx.x, red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
+}
+
+// launch B: pseudo_weight_kernel's value per map, ClassMix'd against ones (dacs.py:631-651, :760-761)
+__global__ void split_weights_kernel(const int* __restrict__ count, const long long* __restrict__ src_label,
+                                     const long long* __restrict__ classes, float* __restrict__ weight, int B, int H, int W, int K, int top,
+                                     int bottom) {
+  const long total = (long)B * H * W;
+  const float v0 = (float)((double)count[0] / (double)total), v1 = (float)((double)count[1] / (double)total);
+  const unsigned HW = (unsigned)H * (unsigned)W;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const unsigned iu = (unsigned)i, b = iu / HW, Y = (iu - b * HW) / (unsigned)W;   // (32-bit: B*H*W < 2^31, checked by the launcher)
+    const long long lab = src_label[i];
+    int msk = 0;
+    for (int k = 0; k < K; ++k) msk += (classes[(long)b * K + k] == lab) ? 1 : 0;
+    const bool edge = (int)Y < top || (int)Y >= H - bottom;
+    weight[i] = msk ? 1.f : (edge ? 0.f : v0);
+    weight[total + i] = msk ? 1.f : (edge ? 0.f : v1);
+  }
+}
+
 static inline int grid_for(long n) { return (int)std::max<long>(1, std::min<long>((n + 255) / 256, 4096)); }
 }  // namespace
 
@@ -570,5 +648,32 @@ extern "C" int cmda_upsample_logits_nchw(const float* logits, float* out, int B,
   if ((long)B * H * W >= (1L << 32)) return CMDA_ERR_SHAPE;   // (32-bit index arithmetic in the kernel)
   CMDA_LAUNCH(upsample_logits_nchw_kernel, dim3(grid_for((long)B * H * W)), dim3(256), 0, stream, logits, out, B, h, w,
               H, W, nc);
+  CMDA_CHECK_LAUNCH();
+}
+
+// ---- the sixth ABI table (include/cmda_hip_ext6.h): the split train type's per-stream targets
+extern "C" int cmdax6_abi_version(void) { return 1; }
+
+extern "C" int cmdax6_split_targets(const float* logits0, const float* logits1, const int64_t* src_label, const int64_t* classes,
+                                    int64_t* pseudo, int64_t* mixed, int* count, int B, int h, int w, int H, int W, int nc, int K, float thr,
+                                    void* stream) {
+  if (nc < 1 || nc > kMaxClasses || K < 1 || B < 1 || h < 1 || w < 1 || H < 1 || W < 1) return CMDA_ERR_SHAPE;
+  if ((long)B * H * W > 0x7fffffffL) return CMDA_ERR_SHAPE;
+  if (!logits0 || !logits1 || !src_label || !classes || !pseudo || !mixed || !count) return CMDA_ERR_UNSUPPORTED;
+  const long tiles = (long)B * ((W + kTW - 1) / kTW) * ((H + kTH - 1) / kTH);   // (<= B*H*W: fits the grid)
+  CMDA_LAUNCH(split_targets_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, logits0, logits1, (const long long*)src_label,
+              (const long long*)classes, (long long*)pseudo, (long long*)mixed, count, B, h, w, H, W, nc, K, thr);
+  CMDA_CHECK_LAUNCH();
+}
+
+extern "C" int cmdax6_split_weights(const int* count, const int64_t* src_label, const int64_t* classes, float* weight, int B, int H, int W,
+                                    int K, int top, int bottom, void* stream) {
+  if (K < 1 || B < 1 || H < 1 || W < 1 || top < 0 || bottom < 0) return CMDA_ERR_SHAPE;
+  if ((long)B * H * W > 0x7fffffffL) return CMDA_ERR_SHAPE;
+  if (!count || !src_label || !classes || !weight) return CMDA_ERR_UNSUPPORTED;
+  top = std::min(top, H);
+  bottom = std::min(bottom, H);   // (H - bottom stays inside int whatever the caller passes)
+  CMDA_LAUNCH(split_weights_kernel, dim3(grid_for((long)B * H * W)), dim3(256), 0, stream, count, (const long long*)src_label,
+              (const long long*)classes, weight, B, H, W, K, top, bottom);
   CMDA_CHECK_LAUNCH();
 }

@@ -266,17 +266,19 @@ class _HeadBase(nn.Module):
         return dfs
 
     # classifier: (Dropout2d) -> 1x1 conv, logits fp32 NHWC
-    def _cls_fwd(self, feat, B, H, W, with_dropout=True, drop_B=None):
+    def _cls_fwd(self, feat, B, H, W, with_dropout=True, drop_B=None, conv=None, tag=''):
         """drop_B: only the first drop_B samples get Dropout2d (the image branch of a grouped pass; decode_head.py:570-586:
-        cls_seg has the dropout, cls_seg_events / _fusion do not)"""
+        cls_seg has the dropout, cls_seg_events / _fusion do not -- unless the head has split classifiers).
+        conv: the classifier to use (None: conv_seg); tag: suffix of the branch's dropout hooks ('' image, '_events')"""
+        conv = self.conv_seg if conv is None else conv
         M, Ch = B * H * W, self.channels
         mask = None
         if with_dropout and self.training and self.dropout_ratio > 0 and getattr(self, 'stochastic', True):
             keep = 1.0 - self.dropout_ratio
-            forced = getattr(self, 'inject_dropout_mask', None)   # tests: the oracle's Dropout2d mask [drop_B or B, Ch] of 0/1
+            forced = getattr(self, 'inject_dropout_mask' + tag, None)   # tests: the oracle's Dropout2d mask [drop_B or B, Ch] of 0/1
             nb = B if drop_B is None else drop_B
             m = (torch.rand(nb, Ch, device=feat.device) < keep).float() if forced is None else forced.to(feat.device).float()
-            rt.tap(('dropout2d', getattr(self, '_tap_name', type(self).__name__)), m)
+            rt.tap(('dropout2d', getattr(self, '_tap_name', type(self).__name__) + tag), m)
             m = m / keep
             if nb < B:
                 mask = torch.ones(B, Ch, dtype=torch.float32, device=feat.device)
@@ -286,26 +288,27 @@ class _HeadBase(nn.Module):
             featd = ops.sample_scale(feat, mask, B, Ch, per_channel=True)
         else:
             featd = feat
-        logits = K.linear_fwd(featd, self.conv_seg.weight, self.conv_seg.bias, M, Ch,
+        logits = K.linear_fwd(featd, conv.weight, conv.bias, M, Ch,
                               out_dtype=torch.float32)
-        return logits.view(B, H, W, self.num_classes), (featd, mask)
+        return logits.view(B, H, W, self.num_classes), (featd, mask, conv)
 
     def _cls_bwd(self, saved, dlogits, B, H, W):
-        featd, mask = saved
+        """saved: what `_cls_fwd` returned, the classifier it used included"""
+        featd, mask, conv = saved
         M, Ch = B * H * W, self.channels
         dl = dlogits.view(M, self.num_classes)
         nc = self.num_classes
         if rt.compute_dtype() == torch.float32:
-            dfeat = K.linear_bwd(dl, featd, self.conv_seg.weight, self.conv_seg.bias, M, Ch)
+            dfeat = K.linear_bwd(dl, featd, conv.weight, conv.bias, M, Ch)
         elif nc % 8 == 0:
-            dfeat = K.linear_bwd(ops.cast(dl, rt.compute_dtype()), featd, self.conv_seg.weight, self.conv_seg.bias, M, Ch)
+            dfeat = K.linear_bwd(ops.cast(dl, rt.compute_dtype()), featd, conv.weight, conv.bias, M, Ch)
         else:
             # 19 classes: rows of 38 bytes would send both GEMMs to the register-staged kernel (141 + 180 us at 262144 pixels); the
             # cast that had to run anyway pads the rows to 32 columns of zeros instead, the classifier weight keeps its 19 rows (the
             # operand views read zero past them)
             ncp = (nc + 31) // 32 * 32
             dlp = ops.cast_pad_cols(dl, ncp, rt.compute_dtype())
-            w, b = self.conv_seg.weight, self.conv_seg.bias
+            w, b = conv.weight, conv.bias
             dlv = ops.plain_view(dlp, M, ncp)
             ops.gemm(dlv, ops.plain_view(featd, M, Ch), rt.grad(w).view(nc, Ch), nc, Ch, M, a_kstrided=True, b_kstrided=True, dtype=rt.tag(),
                      atomic=True, splits=0, colsum=rt.grad(b), defer=True, keep=(dlp, featd))
@@ -366,16 +369,35 @@ class DAFormerHead(_HeadBase):
 @HEADS.register_module()
 class DAFormerHeadFusion(_HeadBase):
     """daformer_head.py:200-322 + BaseDecodeHeadFusion.forward_train decode_head.py:423-534 (the loss mix used by
-    configs/fusion/*: not `cal_confidence`, not the `_split` train types)."""
+    configs/fusion/* and the split mix of :501-507; not `cal_confidence`).
+
+    Split train type 'cs2dz_image+raw-isr_split' (decode_head.py:318-330, :563-586): `split_cls`; the events branch has its own
+    classifier `conv_seg_events` behind its own Dropout2d (drawn after the image branch's), and the head owns `conv_seg_fusion`, which
+    nothing reads -- no fusion features exist for this type -- and which therefore never gets a gradient (with share_decoder=False the
+    same holds for `embed_layers_fusion` / `fuse_layer_fusion`).  `fwd_train` takes the ground truth and the pixel weights as one
+    tensor or as a dict {'image', 'events'} (a None weight means ones) and mixes loss_seg = L_image * 0.5 * 2 + L_events * 0.5 * 2 in
+    that fp32 order; acc_seg is the image branch's.  The joint (batched) decoder pass is not extended to two classifiers:
+    `joint_ok()` is false for a split head.
+    'cs2dz_image+raw-isr_no-fusion' stays refused: the reference cannot run it (see the assert below)."""
+
+    SPLIT_TYPE = 'cs2dz_image+raw-isr_split'
 
     def __init__(self, **kwargs):
         dp = kwargs['decoder_params']
         assert 'train_type' in dp
         self.train_type = dp['train_type']
-        assert self.train_type not in ('cs2dz_image+raw-isr_split', 'cs2dz_image+raw-isr_no-fusion'), \
-            'split-classifier train types are outside the hot path (SURVEY.md section 2, row 12)'
+        assert self.train_type != 'cs2dz_image+raw-isr_no-fusion', \
+            ("'cs2dz_image+raw-isr_no-fusion' cannot run in the reference: dacs.py:809 calls extract_feat(image=None, events=mixed_isr) "
+             "without cfg, and encoder_decoder.py:703 then evaluates cfg.keys() on None")
         super().__init__(input_transform='multiple_select', **kwargs)
-        self.split_cls = False
+        self.split_cls = self.train_type == self.SPLIT_TYPE
+        if self.split_cls:
+            # decode_head.py:321-326; state-dict keys as there, initialised like conv_seg
+            self.conv_seg_events = nn.Conv2d(self.channels, self.num_classes, kernel_size=1)
+            self.conv_seg_fusion = nn.Conv2d(self.channels, self.num_classes, kernel_size=1)
+            for conv in (self.conv_seg_events, self.conv_seg_fusion):
+                nn.init.normal_(conv.weight, std=0.01)
+                nn.init.zeros_(conv.bias)
         self.share_decoder = bool(dp.get('share_decoder'))
         self.half_share_decoder = bool(dp.get('half_share_decoder'))
         assert not (self.share_decoder and self.half_share_decoder)
@@ -390,6 +412,14 @@ class DAFormerHeadFusion(_HeadBase):
             self.fuse_layer_events = self.fuse_layer_image
             self.embed_layers_fusion = self.embed_layers_image
             self.fuse_layer_fusion = self.fuse_layer_image
+        if self.split_cls:
+            # what no pass of this train type reads: conv_seg_fusion and whatever of the fusion decoder is not shared with a stream.
+            # No gradient ever reaches these; optim.FlatAdamW keeps marked parameters out of its update (weight decay included)
+            read = {id(p) for m in (self.conv_seg, self.conv_seg_events, *self._layers('image'), *self._layers('events'))
+                    for p in m.parameters()}
+            for p in self.parameters():
+                if id(p) not in read:
+                    p._cmda_unread = True
 
     _BRANCHES = (('image_output', 'f_image', 'image', True), ('events_output', 'f_events', 'events', False),
                  ('fusion_output', 'f_fusion', 'fusion', False), ('img_self_res_output', 'f_img_self_res', 'events', False))
@@ -409,7 +439,11 @@ class DAFormerHeadFusion(_HeadBase):
             emb, fuse = self._layers(which)
             feat, sv_b = self._branch_fwd(emb, fuse, feats, B)
             H, W = sv_b[2], sv_b[3]
-            logits, sv_c = self._cls_fwd(feat, B, H, W, with_dropout=dropout)
+            if self.split_cls and which == 'events':   # cls_seg_events with split classifiers: dropout_events, conv_seg_events
+                logits, sv_c = self._cls_fwd(feat, B, H, W, with_dropout=True, conv=self.conv_seg_events, tag='_events')
+            else:
+                assert not (self.split_cls and which == 'fusion'), 'the split train type has no fusion features'
+                logits, sv_c = self._cls_fwd(feat, B, H, W, with_dropout=dropout)
             out[key] = logits
             saved[key] = (sv_b, sv_c, H, W, which)
         return out, saved
@@ -437,7 +471,7 @@ class DAFormerHeadFusion(_HeadBase):
     _REF_ORDER = ('image', 'events', 'fusion', 'isr')   # order forward() runs the branches in (daformer_head.py:305-319)
 
     def joint_ok(self):
-        return self.share_decoder and isinstance(self.fuse_layer_image, ASPPWrapper)
+        return self.share_decoder and isinstance(self.fuse_layer_image, ASPPWrapper) and not self.split_cls
 
     @ops.sited('head')
     def fwd_joint(self, joint, names, B, passes=1):
@@ -472,17 +506,31 @@ class DAFormerHeadFusion(_HeadBase):
         return self._branch_bwd(emb, fuse, sv_b, dfeat, G * P * B)
 
     def _loss_mix(self, logits, gt, seg_weight, cfg):
-        """BaseDecodeHeadFusion.forward_train's loss mix, decode_head.py:508-528"""
+        """BaseDecodeHeadFusion.forward_train's loss mix, decode_head.py:480-528.  gt / seg_weight: a tensor, or a dict
+        {'image', 'events'} with one entry per stream (:481-499; the image and the events branch only: no other branch may exist)"""
         lw = cfg['loss_weight']
         ii, lwt = self.ignore_index, self.loss_decode.loss_weight
+        gts = gt if isinstance(gt, dict) else {'image': gt, 'events': gt}
         if seg_weight is None:
-            seg_weight = torch.ones(gt.shape[0], gt.shape[2], gt.shape[3], dtype=torch.float32, device=gt.device)
+            g0 = gts['image']
+            seg_weight = torch.ones(g0.shape[0], g0.shape[2], g0.shape[3], dtype=torch.float32, device=g0.device)
+        wts = seg_weight if isinstance(seg_weight, dict) else {'image': seg_weight, 'events': seg_weight}
+        if isinstance(gt, dict):
+            assert logits['img_self_res_output'] is None and logits['fusion_output'] is None   # (:496-497)
+        stream = {'image_output': 'image', 'events_output': 'events', 'fusion_output': 'image', 'img_self_res_output': 'events'}
         terms, sv_l = {}, {}
         for key in ('image_output', 'events_output', 'fusion_output', 'img_self_res_output'):
             if logits[key] is not None:
-                loss, acc, sv = ce_losses_fwd(logits[key], gt, seg_weight, ii, lwt)
+                # (fusion takes the plain weight, the ISR branch the events weight, :512 / :519 -- one tensor unless a dict came in)
+                loss, acc, sv = ce_losses_fwd(logits[key], gts[stream[key]], wts[stream[key]], ii, lwt)
                 terms[key] = (loss, acc)
                 sv_l[key] = sv
+        if self.split_cls:
+            # decode_head.py:501-507
+            assert lw['image'] == 0.5 and lw['events'] == 0.5, "the split train type needs loss_weight image = events = 0.5"
+            total = terms['image_output'][0] * lw['image'] * 2 + terms['events_output'][0] * lw['events'] * 2
+            coef = {'image_output': lw['image'] * 2, 'events_output': lw['events'] * 2}
+            return {'loss_seg': total, 'acc_seg': terms['image_output'][1]}, sv_l, coef
         coef = {'image_output': lw['image']}
         if 'fusion_output' in terms:
             coef['fusion_output'] = lw['fusion']

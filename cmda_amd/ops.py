@@ -1463,3 +1463,32 @@ def events_norm_batch(grids, clip_ranges, final_range=1.0):
     call('cmdax5_events_norm_batch', ptr(grids), ptr(out), ptr(ws), c_i32(B), c_i64(n), clips, c_f32(final_range),
          stream_of(grids))
     return out
+
+
+# ---------------------------------------------------------------------------------------------- sixth ABI table (cmda_hip_ext6.h)
+def split_mix_targets(logits_image, logits_events, src_label, classes, thr, top=0, bottom=0):
+    """The split train type's targets ('cs2dz_image+raw-isr_split', dacs.py:628-651, :759-763) for both streams in two launches and
+    one memset: logits_image / logits_events fp32 NHWC [B,h,w,nc] (the teacher's two outputs), src_label int64 [B,H,W], classes
+    int64 [B,K] padded with -1.  Returns (pseudo int64 [2,B,H,W], count int32 [2], mixed int64 [2,B,H,W], weight fp32 [2,B,H,W]);
+    index 0 = image, 1 = events.  Each half equals pseudo_label -> pseudo_weight -> class_mix_label / class_mix (against ones) on
+    that map, bit for bit."""
+    check_dev(logits_image, logits_events, src_label, classes)
+    if logits_image.shape != logits_events.shape or logits_image.dtype != torch.float32 or logits_events.dtype != torch.float32:
+        raise L.CmdaError('split_mix_targets: two fp32 logit maps of one shape')
+    if src_label.dtype != torch.int64 or classes.dtype != torch.int64:
+        raise L.CmdaError('split_mix_targets: int64 labels and classes')
+    B, h, w, nc = logits_image.shape
+    _, H, W = src_label.shape
+    if src_label.shape[0] != B or classes.dim() != 2 or classes.shape[0] != B:
+        raise L.CmdaError('split_mix_targets: labels [B,H,W] and classes [B,K] of the logits\' batch')
+    dev = logits_image.device
+    pseudo = torch.empty(2, B, H, W, dtype=torch.int64, device=dev)
+    mixed = torch.empty(2, B, H, W, dtype=torch.int64, device=dev)
+    weight = torch.empty(2, B, H, W, dtype=torch.float32, device=dev)
+    count = torch.zeros(2, dtype=torch.int32, device=dev)
+    K = classes.shape[1]
+    call('cmdax6_split_targets', ptr(logits_image), ptr(logits_events), ptr(src_label), ptr(classes), ptr(pseudo), ptr(mixed), ptr(count),
+         c_i32(B), c_i32(h), c_i32(w), c_i32(H), c_i32(W), c_i32(nc), c_i32(K), c_f32(thr), stream_of(logits_image))
+    call('cmdax6_split_weights', ptr(count), ptr(src_label), ptr(classes), ptr(weight), c_i32(B), c_i32(H), c_i32(W), c_i32(K),
+         c_i32(top), c_i32(bottom), stream_of(logits_image))
+    return pseudo, count, mixed, weight

@@ -42,10 +42,18 @@ class FlatAdamW:
         # inside a group, parameters sit in the order their gradients become final in the backward pass (decode head, then
         # backbone stage 4 ... 1), so each stage's weights are ONE contiguous slice the all-reduce can start on early
         uniq.sort(key=lambda np_: _backward_rank(np_[0]))
-        groups = {}
+        # Parameters no forward pass reads (marked `_cmda_unread` by their module: the split decode head's conv_seg_fusion and, without a
+        # shared decoder, its fusion branch) never get a gradient; torch's AdamW skips a parameter whose .grad is None, weight decay
+        # included.  Here every slot has a gradient (zeros), so these live behind the last update segment: in the flat store (state
+        # dict, EMA teacher, bf16 mirror) but inside no segment -- no update ever touches them.
+        groups, unread = {}, []
         for n, p in uniq:
-            groups.setdefault(_group_of(n, custom_keys), []).append(p)
+            if getattr(p, '_cmda_unread', False):
+                unread.append(p)
+            else:
+                groups.setdefault(_group_of(n, custom_keys), []).append(p)
         self._names = {id(p): n for n, p in uniq}
+        self._custom_keys = custom_keys
         self._order = [p for _, p in named if id(p) in seen]          # model.named_parameters() order, unique
         self._order = list({id(p): p for p in self._order}.values())
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
@@ -56,9 +64,10 @@ class FlatAdamW:
         self.flat_m = torch.zeros(total, dtype=torch.float32, device=dev)
         self.flat_v = torch.zeros(total, dtype=torch.float32, device=dev)
         self.segments = []  # (start, end, lr_mult, decay_mult)
+        self.unread_range = None   # [start, end) of the never-read parameters' slots
         off = 0
         with torch.no_grad():
-            for (lm, dm), ps in sorted(groups.items()):
+            for (lm, dm), ps in sorted(groups.items()) + ([((None, None), unread)] if unread else []):
                 start = off
                 for p in ps:
                     n = p.numel()
@@ -77,7 +86,10 @@ class FlatAdamW:
                         p.data = self.flat_p[off:off + n].view(p.shape)
                         p.grad = self.flat_g[off:off + n].view(p.shape)
                     off += (n + 7) // 8 * 8
-                self.segments.append((start, off, lm, dm))
+                if lm is None:
+                    self.unread_range = (start, off)
+                else:
+                    self.segments.append((start, off, lm, dm))
         # bf16 compute copies of every parameter, kept current by the AdamW kernel itself (no per-step cast launches)
         self.flat_bf16 = None
         if rt.compute_dtype() == torch.bfloat16 and self.flat_p.is_cuda:
@@ -196,11 +208,13 @@ class FlatAdamW:
         model.named_parameters() order, one group per parameter (mmcv's DefaultOptimizerConstructor with paramwise_cfg builds
         one group per parameter), tensors on the CPU."""
         state, groups = {}, []
-        seg_of = lambda o: next((lm, dm) for s, e, lm, dm in self.segments if s <= o < e)  # noqa: E731
+        seg_of = lambda o: next(((lm, dm) for s, e, lm, dm in self.segments if s <= o < e), None)  # noqa: E731
         for i, p in enumerate(self._order):
             lo, hi = self._slot(p)
-            lm, dm = seg_of(lo)
-            if self.step_count > 0:
+            seg = seg_of(lo)
+            # (a never-read parameter: its group is listed, it has no state -- as with torch's AdamW and a .grad of None)
+            lm, dm = seg if seg is not None else _group_of(self._names[id(p)], self._custom_keys)
+            if self.step_count > 0 and seg is not None:
                 state[i] = {'step': self.step_count, 'exp_avg': _slot_view(self.flat_m, lo, p).detach().cpu().contiguous().clone(),
                             'exp_avg_sq': _slot_view(self.flat_v, lo, p).detach().cpu().contiguous().clone()}
             groups.append({'lr': self.lr * lm, 'betas': tuple(self.betas), 'eps': self.eps, 'weight_decay': self.weight_decay * dm,

@@ -449,7 +449,9 @@ def _sum_grads(a, b):
 @SEGMENTORS.register_module()
 class FusionEncoderDecoder(nn.Module):
     """encoder_decoder.py:625-1003 for train types 'cs2dsec_image+events_together' / 'cs2dsec_image+events' /
-    'cs2dz_image+raw-isr' (the ones configs/fusion/* use)."""
+    'cs2dz_image+raw-isr' (the ones configs/fusion/* use) and the two-stream 'cs2dz_image+raw-isr_split' (no fusion module: the
+    image and the ISR stream each end in their own classifier of the decode head; the teacher pass `encode_decode_lowres(image, isr)`
+    returns both outputs, inference reads the events output of `night_isr`, see `_resolve_test_inputs`)."""
 
     TRAIN_TYPES = {'cs2dsec_image+events', 'cs2dz_image+d2n-isr', 'cs2dz_image+raw-isr', 'cs2dz_image+raw-isr_no-fusion',
                    'cs2dz_image+raw-isr_split', 'cs2dsec_image+events_together'}
@@ -710,9 +712,14 @@ class FusionEncoderDecoder(nn.Module):
         return ops.upsample_logits_nchw(out[test_cfg['output_type'] + '_output'], H, W)
 
     def _resolve_test_inputs(self, kwargs):
-        """(img, events, test_cfg of encode_decode) from the keyword inputs of the test pipeline (encoder_decoder.py:897-930)"""
+        """(img, events, test_cfg of encode_decode) from the keyword inputs of the test pipeline (encoder_decoder.py:897-930).
+        Split train type (:903-904, :919-920): the events are `night_isr` (required) and the output is the events branch's."""
         img = kwargs['warp_image'] if 'warp_image' in kwargs else kwargs['image']
         test_cfg = kwargs.get('test_cfg') or {'output_type': 'fusion'}
+        if self.train_type == 'cs2dz_image+raw-isr_split':
+            if kwargs.get('night_isr') is None:
+                raise KeyError("night_isr: the train type 'cs2dz_image+raw-isr_split' predicts from the ISR stream; pass night_isr=...")
+            return img, kwargs['night_isr'], {'output_type': 'events'}
         if self.train_type in {'cs2dsec_image+events', 'cs2dsec_image+events_together'} and 'events_vg' in kwargs:
             events = kwargs['events_vg']
         elif self.train_type == 'cs2dz_image+raw-isr' and test_cfg['output_type'] == 'image_isr':
@@ -723,10 +730,17 @@ class FusionEncoderDecoder(nn.Module):
             test_cfg = {'output_type': 'fusion'} if test_cfg['output_type'] == 'image_isr' else {'output_type': 'image'}
         return img, events, test_cfg
 
+    def _net_image(self, img):
+        """the image the network gets at test time.  Split train type: None -- the reference runs the image stream too and discards its
+        output (encode_decode with output_type 'events'); in eval mode that stream has no side effect (BatchNorm reads its running
+        statistics, DropPath / Dropout2d are off, nothing joins the two streams), so only the event encoder and the events decoder
+        branch run here and the result is exactly the same."""
+        return None if self.train_type == 'cs2dz_image+raw-isr_split' else img
+
     def whole_inference(self, rescale, **kwargs):
         """encoder_decoder.py:897-936: logits at the input size, resized once more to img_metas['ori_shape'] when `rescale`"""
         img, events, test_cfg = self._resolve_test_inputs(kwargs)
-        seg_logit = self.encode_decode(img, events, test_cfg=test_cfg)
+        seg_logit = self.encode_decode(self._net_image(img), events, test_cfg=test_cfg)
         if rescale and kwargs.get('img_metas') is not None:
             seg_logit = _resize_logits(seg_logit, _first_meta(kwargs['img_metas'])['ori_shape'])
         return seg_logit
@@ -738,7 +752,7 @@ class FusionEncoderDecoder(nn.Module):
         img, events, test_cfg = self._resolve_test_inputs(kwargs)
         key = ('image' if events is None else test_cfg['output_type']) + '_output'   # (encode_decode's rule)
         spatial = {'img': img} if events is None else {'img': img, 'events': events}
-        return (spatial, (lambda s: self.encode_decode_lowres(s['img'], s.get('events'), None, test_cfg)[key]),
+        return (spatial, (lambda s: self.encode_decode_lowres(self._net_image(s['img']), s.get('events'), None, test_cfg)[key]),
                 _first_meta(kwargs.get('img_metas')))
 
     def slide_inference(self, rescale, **kwargs):

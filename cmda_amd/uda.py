@@ -17,8 +17,18 @@ work runs, not what is computed:
 The image-only train types 'cs2dsec_image' / 'cs2dz_image' (DAFormer's DACS on one MiT and a plain DAFormerHead, the baseline the
 fusion types are compared against; dacs.py:363-377 and the image branches below) run through `_iteration_image`: no events, no ISR,
 no fusion; for 'cs2dz_image' optionally the frozen 3 -> 3 day -> night generator on the source image (cyclegan_id2in_path).
-Out of scope here: the remaining train types ('cs2dz_image+d2n-isr', '_split', '_no-fusion'), OrgDACS,
-LightNet (cyclegan_light_path), the matplotlib debug panels, flare / cow-mask / deflare augmentations.
+The split train type 'cs2dz_image+raw-isr_split' (two-stream co-training on Dark Zurich without a fusion block, the ablation row the
+fusion result is compared against; dacs.py:611-651, :716-771, :797-802) runs through `_iteration` with the inputs, the mixed image /
+ISR and the ISR augmentations of 'cs2dz_image+raw-isr': the teacher's image and events outputs each give their own pseudo-labels,
+confident-pixel share and weight map (`ops.split_mix_targets`: both streams' targets in one kernel pair, one class draw shared), and the
+mixed step trains each stream on its own targets (dict labels / weights into DAFormerHeadFusion's split loss); the source step passes
+the plain label to both streams.  The student runs the two-pass route (no fusion module: no joint pass), on the same lanes.
+Refused, with the reason, at construction: 'cs2dz_image+raw-isr_no-fusion' (the reference cannot run it: dacs.py:809 calls
+extract_feat(image=None, events=mixed_isr) without cfg and encoder_decoder.py:703 then evaluates cfg.keys() on None),
+'cs2dz_image+d2n-isr' (needs pre-translated ISR files that no loader here produces), and the split type together with the ImageNet
+feature distance (dacs.py:568-575 ends in an assert for it).
+Out of scope here: OrgDACS, LightNet (cyclegan_light_path), the matplotlib debug panels, flare / cow-mask /
+deflare augmentations.
 ISR augmentations (isr_augment.hip): `sky_mask` (dacs.py:431-434, the source ISR before the student sees it) and `isr_noise_dacs_type`
 (dacs.py:753-755, on the ISR recomputed from the mixed image) run as batched launches whose per-sample draws travel in the control
 block; the noise fields come from a counter-based generator in the kernel (seed fixed at construction, offset = the iteration counter),
@@ -82,13 +92,24 @@ GRAPH_LANES = tuple(x for x in os.environ.get('CMDA_GRAPH_LANES', 'enc,T,Tenc,wq
 
 @UDA.register_module()
 class DACS(nn.Module):
-    SUPPORTED = {'cs2dsec_image+events', 'cs2dz_image+raw-isr', 'cs2dsec_image+events_together', 'cs2dsec_image', 'cs2dz_image'}
+    SUPPORTED = {'cs2dsec_image+events', 'cs2dz_image+raw-isr', 'cs2dsec_image+events_together', 'cs2dsec_image', 'cs2dz_image',
+                 'cs2dz_image+raw-isr_split'}
+    SPLIT_TYPE = 'cs2dz_image+raw-isr_split'
+    RAW_ISR_TYPES = {'cs2dz_image+raw-isr', 'cs2dz_image+raw-isr_split'}   # Dark Zurich: image + ISR, no events, no generator
+    REFUSED = {'cs2dz_image+raw-isr_no-fusion': 'the reference cannot run it: dacs.py:809 calls extract_feat(image=None, events=mixed_isr) '
+                                                'without cfg, and encoder_decoder.py:703 then evaluates cfg.keys() on None',
+               'cs2dz_image+d2n-isr': 'it needs pre-translated ISR files that no loader here produces'}
     IMAGE_TYPES = {'cs2dsec_image', 'cs2dz_image'}   # image-only: EventsEncoderDecoder, no events / ISR / fusion (_iteration_image)
     # ImageNet mean / std of the image normalisation (get_mean_std): the day -> night generator works on [-1, 1] images
     IMNET_MEAN, IMNET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)
 
     def __init__(self, **cfg):
         super().__init__()
+        if cfg.get('train_type') in self.REFUSED:
+            raise ValueError(f"train_type {cfg['train_type']!r} is refused: {self.REFUSED[cfg['train_type']]}")
+        if cfg.get('train_type') == self.SPLIT_TYPE and cfg['imnet_feature_dist_lambda'] > 0:
+            raise ValueError(f"train_type {self.SPLIT_TYPE!r} with imnet_feature_dist_lambda > 0 is refused: the reference's feature-distance "
+                             "step (dacs.py:568-575) ends in an assert for this train type")
         self.model = build_segmentor(deepcopy(cfg['model']))
         self.train_cfg = cfg['model'].get('train_cfg')
         self.test_cfg = cfg['model'].get('test_cfg')
@@ -116,8 +137,10 @@ class DACS(nn.Module):
         self.train_type = cfg['train_type']
         assert self.train_type in self.SUPPORTED, f'train_type {self.train_type} is outside the accelerated hot path'
         self.image_only = self.train_type in self.IMAGE_TYPES
+        self.split = self.train_type == self.SPLIT_TYPE
         self.forward_cfg = dict(cfg['forward_cfg'])
         self.img_self_res_reg = cfg.get('img_self_res_reg', 'no')
+        assert not self.split or self.img_self_res_reg == 'no', "the split train type needs img_self_res_reg 'no' (dacs.py:538)"
         path = cfg.get('cyclegan_itrd2en_path', '')
         self.cyclegan_itrd2en = None
         if path and self.train_type in {'cs2dsec_image+events', 'cs2dsec_image+events_together'}:
@@ -194,6 +217,7 @@ class DACS(nn.Module):
         # switches that bench.py, the tests and tools/ set from outside
         self.fused_student_passes = True   # source + mixed samples as ONE student pass where the segmentor can (_iteration)
         self.early_student = True          # the EARLY-STUDENT schedule of _iteration (needs lane 'T')
+        self.split_fused_targets = True    # split train type: both streams' targets from ops.split_mix_targets (else _mix_targets twice)
         self.graph_lanes = True            # the captured iteration runs on concurrency lanes ...
         self.graph_lane_set = None         # ... these (None: CMDA_LANES, else GRAPH_LANES)
         self.final_pass_grad_hook = None   # runtime.grad_ready_hook during the step's last backward pass (data-parallel drivers)
@@ -357,7 +381,7 @@ class DACS(nn.Module):
         d = {}
         if self.image_only:
             d['choice'] = None   # (no events / ISR choice: the torch.rand of dacs.py:414-417 is in the events branch only)
-        elif self.train_type == 'cs2dz_image+raw-isr':
+        elif self.train_type in self.RAW_ISR_TYPES:
             d['choice'] = 0.0
         elif self.without_events:
             d['choice'] = -1.0
@@ -534,6 +558,20 @@ class DACS(nn.Module):
         mixed_weight = ops.class_mix(gt_pixel_weight.view(B, 1, H, W), pseudo_weight.view(B, 1, H, W), lab, classes).view(B, H, W)
         return pseudo_label, count, mixed_lbl, mixed_weight
 
+    def _split_targets(self, logits_image, logits_events, lab, classes):
+        """the split train type's `_mix_targets`: (pseudo [2,B,H,W], count [2], mixed labels {'image', 'events'} [B,1,H,W], mixed weights
+        {'image', 'events'} [B,H,W]); one class draw serves both streams (dacs.py:719-763)"""
+        B, H, W = lab.shape
+        if self.split_fused_targets:
+            pseudo, count, mixed, weight = ops.split_mix_targets(logits_image, logits_events, lab, classes, self.pseudo_threshold,
+                                                                 self.psweight_ignore_top, self.psweight_ignore_bottom)
+        else:   # the composed sequence, per stream
+            parts = [self._mix_targets(lg, lab, classes) for lg in (logits_image, logits_events)]
+            pseudo, count = torch.stack([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+            mixed, weight = torch.stack([p[2].view(B, H, W) for p in parts]), torch.stack([p[3] for p in parts])
+        return (pseudo, count, {'image': mixed[0].view(B, 1, H, W), 'events': mixed[1].view(B, 1, H, W)},
+                {'image': weight[0], 'events': weight[1]})
+
     def _mixed_image(self, day_image, night_image, lab, classes, ctl):
         """ClassMix + strong augmentation (dacs.py:716-724; dacs_transforms.py:64-98, kornia semantics): the on/off gates and the
         per-sample parameters are read from the control block by the kernels"""
@@ -600,7 +638,8 @@ class DACS(nn.Module):
         ext_wait = self._ext_wait()
         day_image, day_isr, day_label = src['image'], src['img_self_res'], src['label']
         day_events = night_events = None
-        if tt == 'cs2dz_image+raw-isr':
+        raw_isr = tt in self.RAW_ISR_TYPES
+        if raw_isr:
             night_image = tgt['warp_image'] if 'warp_image' in tgt else tgt['image']
         else:
             night_image, night_events = tgt['warp_image'], tgt['events_vg']
@@ -625,12 +664,14 @@ class DACS(nn.Module):
 
         def teacher_labels():
             """teacher forward -> pseudo-labels -> ClassMix'd labels / weights (dacs.py:653-711, :716-771 for the targets)"""
-            if tt != 'cs2dz_image+raw-isr' and self.fuse_both_ice_and_e:
+            if not raw_isr and self.fuse_both_ice_and_e:
                 ema = teacher.encode_decode_lowres(night_image, night_events, tgt['warp_img_self_res'], dict(self.forward_cfg, fusion_all=True))
-            elif tt != 'cs2dz_image+raw-isr' and self.isr_another_fusion and not use_events:
+            elif not raw_isr and self.isr_another_fusion and not use_events:
                 ema = teacher.encode_decode_lowres(night_image, teacher_second, test_cfg=dict(self.forward_cfg, fusion_isr=True))
             else:
                 ema = teacher.encode_decode_lowres(night_image, teacher_second, test_cfg=self.forward_cfg)
+            if self.split:   # dacs.py:628-651, :759-763: each stream's output gives that stream's targets
+                return (ema,) + self._split_targets(ema['image_output'], ema['events_output'], lab, classes)
             return (ema,) + self._mix_targets(ema['fusion_output'], lab, classes)
 
         def mixed_inputs():
@@ -658,7 +699,7 @@ class DACS(nn.Module):
         # OVERLAPPED UPDATE (FlatAdamW.overlap): AdamW, the gradient clear and the EMA update of the step boundary run on the optimizer's
         # own stream; the part of the iteration that reads no trainable weight -- the mixed inputs and the frozen generator -- is enqueued
         # FIRST and runs underneath them, then this lane waits for that stream (`wait_external`), refreshes the weight copies and goes on.
-        pre = early and ext_wait is not None and tt != 'cs2dz_image+raw-isr' and self.cyclegan_itrd2en is not None
+        pre = early and ext_wait is not None and not raw_isr and self.cyclegan_itrd2en is not None
         day_events_pre = None
         if pre:
             mixed_img, mixed_isr = mixed_inputs()
@@ -685,7 +726,7 @@ class DACS(nn.Module):
                 fd = self._fdist_targets(day_image, day_label)
 
         # ---- Image Motion-Extractor (dacs.py:400-404), frozen, no grad ------------------------------------------------------------
-        if tt != 'cs2dz_image+raw-isr':
+        if not raw_isr:
             if self.cyclegan_itrd2en is not None:
                 # frozen weights, static input: queued behind the teacher's event encoder on the side lane, next to the
                 # teacher's fusion / decoder / pseudo-label / mixing work on this one
@@ -708,7 +749,7 @@ class DACS(nn.Module):
                     mixed_events = ops.class_mix(day_events, night_events, lab, classes)
 
         # ---- student inputs: source (dacs.py:489-523) and mixed (dacs.py:820-860) ---------------------------------------------------
-        if tt == 'cs2dz_image+raw-isr':
+        if raw_isr:
             in_src = {'image': day_image, 'events': day_isr}
             in_mix = {'image': mixed_img, 'events': mixed_isr}
         elif tt == 'cs2dsec_image+events_together':
@@ -745,6 +786,10 @@ class DACS(nn.Module):
         extras = dict(mixed_img=mixed_img, mixed_lbl=mixed_lbl, mixed_isr=mixed_isr, pseudo_weight=mixed_weight,
                       pseudo_label=pseudo_label, classes=classes, mixed_events=mixed_events, day_events=day_events,
                       teacher_logits=ema, pseudo_count=count)
+        if self.split:   # per stream: the plain keys carry the image stream's, `*_events` the events stream's
+            extras.update(mixed_lbl=mixed_lbl['image'], mixed_lbl_events=mixed_lbl['events'], pseudo_weight=mixed_weight['image'],
+                          pseudo_weight_events=mixed_weight['events'], pseudo_label=pseudo_label[0], pseudo_label_events=pseudo_label[1],
+                          pseudo_count=count[0:1], pseudo_count_events=count[1:2])
         if self.sky_bank is not None:
             extras['day_isr'] = day_isr   # the sky-masked source ISR the student saw
         return log_vars, self._with_fdist(extras, fd)
@@ -853,7 +898,7 @@ class DACS(nn.Module):
         self.last_draws = draws
         if not self.image_only:
             self.forward_cfg['isr_events_fusion_choice'] = draws['choice']
-        use_events = not self.image_only and tt != 'cs2dz_image+raw-isr' and draws['choice'] > self.random_choice_thres
+        use_events = not self.image_only and tt not in self.RAW_ISR_TYPES and draws['choice'] > self.random_choice_thres
         cb = self._control_block(dev, B, H, W)
         self._stage(cb, draws)
         opt = self._opt
@@ -870,7 +915,7 @@ class DACS(nn.Module):
                     self._update_ema(self.local_iter)
         if self.image_only:
             second = None
-        elif tt == 'cs2dz_image+raw-isr':
+        elif tt in self.RAW_ISR_TYPES:
             second = tgt['warp_img_self_res'] if 'warp_image' in tgt else tgt['night_isr']
         else:
             second = tgt['events_vg'] if (use_events or self.isr_no_fusion) else tgt['warp_img_self_res']
