@@ -1,5 +1,6 @@
 """ctypes binding of libcmda_hip.so (the C ABI declared in include/cmda_hip.h and its extensions include/cmda_hip_ext.h,
-include/cmda_hip_ext2.h, include/cmda_hip_ext3.h, include/cmda_hip_ext4.h, include/cmda_hip_ext5.h and include/cmda_hip_ext6.h).
+include/cmda_hip_ext2.h, include/cmda_hip_ext3.h, include/cmda_hip_ext4.h, include/cmda_hip_ext5.h, include/cmda_hip_ext6.h and
+include/cmda_hip_ext7.h).
 
 The product path has exactly one backend: the gfx950 kernel library built in-tree by
 ``__graft_entry__.build()`` / ``make hip``.  If it is missing, or a tensor is not on the GPU,
@@ -26,6 +27,7 @@ ABI_EXT3_VERSION = 1
 ABI_EXT4_VERSION = 1
 ABI_EXT5_VERSION = 1
 ABI_EXT6_VERSION = 1
+ABI_EXT7_VERSION = 1
 
 
 class View(ctypes.Structure):
@@ -109,6 +111,14 @@ def _declare(lib):
     lib.cmdax6_abi_version.restype = ctypes.c_int
     if lib.cmdax6_abi_version() != ABI_EXT6_VERSION:
         raise CmdaError('libcmda_hip.so sixth ABI table (cmdax6_*) version mismatch')
+    # the seventh table (include/cmda_hip_ext7.h): the OHEM pixel sampler and its exact k-th-key select
+    if not hasattr(lib, 'cmdax7_abi_version'):
+        raise CmdaError('the kernel library lacks the seventh ABI table (cmdax7_*): rebuild it')
+    lib.cmdax7_abi_version.restype = ctypes.c_int
+    if lib.cmdax7_abi_version() != ABI_EXT7_VERSION:
+        raise CmdaError('libcmda_hip.so seventh ABI table (cmdax7_*) version mismatch')
+    lib.cmdax7_ws_bytes.restype = ctypes.c_int64
+    lib.cmdax7_ws_bytes.argtypes = [ctypes.c_int64]
     return lib
 
 

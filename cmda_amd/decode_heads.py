@@ -9,13 +9,15 @@ Data layout: every feature map is NHWC flattened to [B*H*W, C]; the four embeds 
 channel slice of one [B*H*W, 1024] buffer (no torch.cat), the four ASPP branches likewise into the bottleneck's input;
 logits stay fp32 NHWC and the 19 x H x W up-sampled tensor of losses() is never materialised (ce_loss.hip).
 """
+import weakref
+
 import torch
 import torch.nn as nn
 
 from . import nn as K
 from . import deferred, ops
 from . import runtime as rt
-from .registry import HEADS, LOSSES, build_loss
+from .registry import HEADS, LOSSES, PIXEL_SAMPLERS, build_loss, build_pixel_sampler
 
 
 # ---------------------------------------------------------------------------------------------- containers
@@ -169,6 +171,44 @@ class CrossEntropyLoss(nn.Module):
         self.loss_weight, self.class_weight = loss_weight, class_weight
 
 
+@PIXEL_SAMPLERS.register_module()
+class OHEMPixelSampler:
+    """mmseg/core/seg/sampler/ohem_pixel_sampler.py on the device (ops.ohem_weight: keys from the tiled up-sample-and-score kernel, an
+    exact radix select of the one order statistic the reference sorts for, no host synchronisation).  `context`: the decode head
+    (its ignore_index).  thresh a float: the pixels whose label probability is below max(thresh, the min_kept * B-th smallest); thresh
+    None: the min_kept * B pixels of largest loss -- where several pixels tie exactly at that boundary ALL of them are taken (the
+    reference's unstable sort keeps an unspecified subset).  Labels outside [0, num_classes) are invalid like ignore_index (the
+    reference's gather would fail on them)."""
+
+    def __init__(self, context, thresh=None, min_kept=100000):
+        assert min_kept > 1
+        # The head is held WEAKLY: head -> sampler -> head would be a reference cycle, and a model in a cycle is freed by the cyclic
+        # collector at some later allocation instead of when its last name goes -- rt.refresh() then sees the set of live weight
+        # copies change in the middle of a later model's graph capture and has to build a new plan there (a host-to-device copy,
+        # which a capturing stream refuses).
+        self._context = weakref.ref(context)
+        self.thresh, self.min_kept = thresh, min_kept
+
+    @property
+    def context(self):
+        return self._context()
+
+    def __deepcopy__(self, memo):
+        ctx = self.context   # a head copied along with its sampler: the copy's sampler points at the copy
+        return type(self)(memo.get(id(ctx), ctx), self.thresh, self.min_kept)
+
+    def weight(self, logits, seg_label):
+        """the head's own layout: logits fp32 NHWC [B,h,w,nc] at the decoder's resolution, label [B,1,H,W] -> fp32 [B,H,W]"""
+        B, _, H, W = seg_label.shape
+        return ops.ohem_weight(logits, seg_label.view(B, H, W), H, W, self.thresh, self.min_kept, self.context.ignore_index)
+
+    def sample(self, seg_logit, seg_label):
+        """Reference signature: logits (N, C, H, W) at the label's size, label (N, 1, H, W) -> weight (N, H, W)."""
+        assert seg_logit.shape[2:] == seg_label.shape[2:]
+        assert seg_label.shape[1] == 1
+        return self.weight(seg_logit.float().permute(0, 2, 3, 1).contiguous(), seg_label.long().contiguous())
+
+
 def ce_losses_fwd(logits, seg_label, seg_weight, ignore_index, loss_weight):
     """losses(): logits fp32 NHWC [B,h,w,nc]; label [B,1,H,W] int64.  Returns (loss, acc%, saved)."""
     B, _, H, W = seg_label.shape
@@ -194,7 +234,11 @@ class _HeadBase(nn.Module):
                  loss_decode=dict(type='CrossEntropyLoss', use_sigmoid=False, loss_weight=1.0), decoder_params=None,
                  ignore_index=255, sampler=None, align_corners=False, init_cfg=None):
         super().__init__()
-        assert input_transform == 'multiple_select' and sampler is None
+        assert input_transform == 'multiple_select'
+        # decode_head.py:82-85.  With a sampler every loss term takes seg_weight = sampler.sample(that term's logits, its labels) IN
+        # PLACE of the weight the caller passed (:230-231, :597-598): under DACS the pseudo-weight of the mixed pass is discarded, as
+        # in the reference.  The same weight is saved for the backward.  Plain attribute, not a sub-module: it points back at the head.
+        self.sampler = build_pixel_sampler(sampler, context=self) if sampler is not None else None
         assert isinstance(in_channels, (list, tuple)) and isinstance(in_index, (list, tuple))
         assert len(in_channels) == len(in_index)
         assert not align_corners
@@ -351,6 +395,8 @@ class DAFormerHead(_HeadBase):
 
     def fwd_train(self, feats, B, gt, seg_weight=None):
         logits, sv = self.fwd(feats, B)
+        if self.sampler is not None:   # (the incoming weight is discarded: _HeadBase.__init__)
+            seg_weight = self.sampler.weight(logits, gt)
         loss, acc, sv_l = ce_losses_fwd(logits, gt, seg_weight, self.ignore_index, self.loss_decode.loss_weight)
         return {'loss_seg': loss, 'acc_seg': acc}, logits, (sv, sv_l)
 
@@ -507,10 +553,14 @@ class DAFormerHeadFusion(_HeadBase):
 
     def _loss_mix(self, logits, gt, seg_weight, cfg):
         """BaseDecodeHeadFusion.forward_train's loss mix, decode_head.py:480-528.  gt / seg_weight: a tensor, or a dict
-        {'image', 'events'} with one entry per stream (:481-499; the image and the events branch only: no other branch may exist)"""
+        {'image', 'events'} with one entry per stream (:481-499; the image and the events branch only: no other branch may exist).
+        With a sampler each term's weight is the sampler's, from that term's own logits and its stream's labels (:597-598); the
+        incoming seg_weight -- DACS's pseudo-weight of the mixed pass included -- is not read."""
         lw = cfg['loss_weight']
         ii, lwt = self.ignore_index, self.loss_decode.loss_weight
         gts = gt if isinstance(gt, dict) else {'image': gt, 'events': gt}
+        if self.sampler is not None:
+            seg_weight = {'image': None, 'events': None}
         if seg_weight is None:
             g0 = gts['image']
             seg_weight = torch.ones(g0.shape[0], g0.shape[2], g0.shape[3], dtype=torch.float32, device=g0.device)
@@ -522,7 +572,8 @@ class DAFormerHeadFusion(_HeadBase):
         for key in ('image_output', 'events_output', 'fusion_output', 'img_self_res_output'):
             if logits[key] is not None:
                 # (fusion takes the plain weight, the ISR branch the events weight, :512 / :519 -- one tensor unless a dict came in)
-                loss, acc, sv = ce_losses_fwd(logits[key], gts[stream[key]], wts[stream[key]], ii, lwt)
+                wt = wts[stream[key]] if self.sampler is None else self.sampler.weight(logits[key], gts[stream[key]])
+                loss, acc, sv = ce_losses_fwd(logits[key], gts[stream[key]], wt, ii, lwt)
                 terms[key] = (loss, acc)
                 sv_l[key] = sv
         if self.split_cls:
@@ -576,6 +627,8 @@ class DAFormerHeadFusion(_HeadBase):
             sv_l = {}
             for g, nm in enumerate(names):
                 k = self._KEY[nm]
+                if self.sampler is not None:   # this term's own hard pixels, in place of the incoming weight (decode_head.py:597-598)
+                    wgt = self.sampler.weight(lgs[p][k], gts[p])
                 _, lse = ops.ce_upsample_fwd(lgs[p][k], label, wgt, H, W, ii, acc=acc[g * P + p])
                 sv_l[k] = (lgs[p][k], label, wgt, lse, H, W, n)
             sv_ls.append(sv_l)

@@ -1492,3 +1492,60 @@ def split_mix_targets(logits_image, logits_events, src_label, classes, thr, top=
     call('cmdax6_split_weights', ptr(count), ptr(src_label), ptr(classes), ptr(weight), c_i32(B), c_i32(H), c_i32(W), c_i32(K),
          c_i32(top), c_i32(bottom), stream_of(logits_image))
     return pseudo, count, mixed, weight
+
+
+# ---------------------------------------------------------------------------------------------- seventh ABI table (cmda_hip_ext7.h)
+OHEM_THRESH, OHEM_LOSS = 0, 1
+
+
+def _ohem_ws(n_keys, device):
+    nbytes = L.lib().cmdax7_ws_bytes(n_keys)
+    if nbytes < 0:
+        raise L.CmdaError(f'cmdax7_ws_bytes: {n_keys} keys are beyond 2^31 - 1')
+    return torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+
+
+def select_kth(keys, k):
+    """The k-th smallest (from 0) of an fp32 tensor of any shape, exactly: a 1-element fp32 tensor equal to
+    keys.flatten().sort()[0][k].  k: int32 device scalar tensor, read on the device (clamped to [0, n - 1]); nothing synchronises with
+    the host.  Radix select, 4 launches and the clearing of its counters."""
+    check_dev(keys, k)
+    if keys.dtype != torch.float32 or k.dtype != torch.int32 or k.numel() != 1:
+        raise L.CmdaError('select_kth: fp32 keys and a 1-element int32 k')
+    if L.emulated() and k.is_cuda or (not L.emulated() and k.device != keys.device):
+        raise L.CmdaError('select_kth: k on another device than the keys')
+    out = torch.empty(1, dtype=torch.float32, device=keys.device)
+    ws = _ohem_ws(0, keys.device)
+    call('cmdax7_select_kth', ptr(keys), c_i64(keys.numel()), ptr(k), ptr(out), ptr(ws), stream_of(keys))
+    return out
+
+
+def ohem_weight(logits, label, H, W, thresh, min_kept, ignore_index=255, debug=False):
+    """OHEMPixelSampler.sample (mmseg/core/seg/sampler/ohem_pixel_sampler.py:32-78) on the low-resolution logits: fp32 NHWC
+    [B,h,w,nc] -> fp32 0/1 weights [B,H,W] of the hard pixels among the valid ones (label int64 [B,H,W]; ignore_index and labels
+    outside [0, nc) are invalid).  The scores are the bilinear up-sample ce_upsample_fwd sees, bit for bit.
+    thresh a float: hard = probability of the label below max(thresh, the min(min_kept * B, n_valid - 1)-th smallest probability);
+    thresh None: hard = loss at or above the (min_kept * B)-th largest per-pixel cross-entropy (every valid pixel when there are no
+    more than that; pixels that tie with that loss exactly are all taken).
+    Nothing here depends on a device value on the host: safe under graph capture.
+    debug=True: returns (weight, keys fp32 [B,H,W] with NaN at invalid pixels, threshold fp32 [1])."""
+    check_dev(logits, label)
+    if logits.dtype != torch.float32 or logits.dim() != 4:
+        raise L.CmdaError('ohem_weight: fp32 NHWC logits [B,h,w,nc]')
+    B, h, w, nc = logits.shape
+    if label.dtype != torch.int64 or tuple(label.shape) != (B, H, W):
+        raise L.CmdaError(f'ohem_weight: int64 labels [{B},{H},{W}], got {label.dtype} {tuple(label.shape)}')
+    dev = logits.device
+    n = B * H * W
+    weight = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+    thr_out = torch.empty(1, dtype=torch.float32, device=dev) if debug else None
+    ws = _ohem_ws(n, dev)
+    mode = OHEM_LOSS if thresh is None else OHEM_THRESH
+    call('cmdax7_ohem_weight', ptr(logits), ptr(label), ptr(weight), ptr(thr_out), ptr(ws), c_i32(B), c_i32(h), c_i32(w), c_i32(H),
+         c_i32(W), c_i32(nc), c_i32(ignore_index), c_i32(mode), c_f32(0.0 if thresh is None else thresh), c_i32(max(-1, min(int(min_kept), 2 ** 31 - 1))),
+         stream_of(logits))
+    if not debug:
+        return weight
+    first = L.lib().cmdax7_ws_bytes(0) // 4
+    keys = ws[first:first + n].view(torch.float32).view(B, H, W)
+    return weight, keys, thr_out

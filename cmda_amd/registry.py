@@ -49,6 +49,7 @@ MODELS = Registry('models')
 BACKBONES = NECKS = HEADS = LOSSES = SEGMENTORS = UDA = FUSION = MODELS
 DATASETS = Registry('dataset')
 PIPELINES = Registry('pipeline')
+PIXEL_SAMPLERS = Registry('pixel sampler')   # mmseg/core/seg/builder.py:4
 
 
 def build_from_cfg(cfg, registry, default_args=None):
@@ -70,6 +71,11 @@ def build_head(cfg):
 
 def build_loss(cfg):
     return LOSSES.build(cfg)
+
+
+def build_pixel_sampler(cfg, **default_args):
+    """mmseg/core/seg/builder.py:7-9: the head passes itself as `context`"""
+    return PIXEL_SAMPLERS.build(cfg, default_args)
 
 
 def build_fusion(cfg):
