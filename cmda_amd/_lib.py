@@ -1,6 +1,6 @@
 """ctypes binding of libcmda_hip.so (the C ABI declared in include/cmda_hip.h and its extensions include/cmda_hip_ext.h,
-include/cmda_hip_ext2.h, include/cmda_hip_ext3.h, include/cmda_hip_ext4.h, include/cmda_hip_ext5.h, include/cmda_hip_ext6.h and
-include/cmda_hip_ext7.h).
+include/cmda_hip_ext2.h, include/cmda_hip_ext3.h, include/cmda_hip_ext4.h, include/cmda_hip_ext5.h, include/cmda_hip_ext6.h,
+include/cmda_hip_ext7.h and include/cmda_hip_ext8.h).
 
 The product path has exactly one backend: the gfx950 kernel library built in-tree by
 ``__graft_entry__.build()`` / ``make hip``.  If it is missing, or a tensor is not on the GPU,
@@ -28,6 +28,7 @@ ABI_EXT4_VERSION = 1
 ABI_EXT5_VERSION = 1
 ABI_EXT6_VERSION = 1
 ABI_EXT7_VERSION = 1
+ABI_EXT8_VERSION = 1
 
 
 class View(ctypes.Structure):
@@ -46,6 +47,15 @@ class GemmParams(ctypes.Structure):
                 ('dtype', c_i32), ('c_vec_ok', c_i32), ('colsum', c_vp),
                 ('c_patch_ow', c_i32), ('c_patch_kh', c_i32), ('c_patch_kwci', c_i32), ('tile_hint', c_i32), ('c_perm_ci', c_i32), ('c_perm_cells', c_i32),
                 ('res_f32', c_i32), ('colstats_rows', c_i32), ('colstats', c_vp)]
+
+
+class Branch8(ctypes.Structure):   # cmdax8_branch_t
+    _fields_ = [('z', c_vp), ('x', c_vp), ('mean', c_vp), ('rstd', c_vp), ('gamma', c_vp), ('beta', c_vp),
+                ('dz', c_vp), ('dres', c_vp), ('dgamma', c_vp), ('dbeta', c_vp)]
+
+
+class Level8(ctypes.Structure):    # cmdax8_level_t
+    _fields_ = [('br', Branch8 * 2), ('out', c_vp), ('dout', c_vp), ('M', c_i64), ('C', c_i32), ('reserved', c_i32)]
 
 
 class CmdaError(RuntimeError):
@@ -122,6 +132,19 @@ def _declare(lib):
     return lib
 
 
+def _declare_ext8(lib):
+    """the eighth table (include/cmda_hip_ext8.h): the fused BasicBlock tail of ConvertAvgFusion.  Checked apart from `_declare`
+    (whose contract ends with the seventh table); `_load` and `_bind_for_tests` call it right behind it."""
+    if not hasattr(lib, 'cmdax8_abi_version'):
+        raise CmdaError('the kernel library lacks the eighth ABI table (cmdax8_*): rebuild it')
+    lib.cmdax8_abi_version.restype = ctypes.c_int
+    if lib.cmdax8_abi_version() != ABI_EXT8_VERSION:
+        raise CmdaError('libcmda_hip.so eighth ABI table (cmdax8_*) version mismatch')
+    lib.cmdax8_ws_floats.restype = ctypes.c_int64
+    lib.cmdax8_ws_floats.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+    return lib
+
+
 def _load():
     global _lib
     if _lib is not None:
@@ -131,7 +154,7 @@ def _load():
             f'{_LIB_PATH} not found: build the gfx950 kernel library first '
             '(python -c "import __graft_entry__ as g; g.build()" or `make hip`). '
             'cmda_amd has no CPU fallback.')
-    _lib = _declare(ctypes.CDLL(_LIB_PATH))
+    _lib = _declare_ext8(_declare(ctypes.CDLL(_LIB_PATH)))
     if _lib.cmda_abi_version() != ABI_VERSION:
         raise CmdaError('libcmda_hip.so ABI version mismatch')
     return _lib
@@ -140,7 +163,7 @@ def _load():
 def _bind_for_tests(path):
     """TEST ONLY: route the C ABI to the CPU emulator build of the same kernel sources."""
     global _lib, _emulated
-    _lib = _declare(ctypes.CDLL(path))
+    _lib = _declare_ext8(_declare(ctypes.CDLL(path)))
     _emulated = True
     return _lib
 

@@ -11,6 +11,7 @@
 // block.  Variance is accumulated around a per-channel shift (row 0) so the single pass is not cancellation-prone.
 // HBM-bound: stats 1 read, apply 1 read + 1 write, bwd-reduce 2 reads, bwd-apply 2 reads + 1 write of M*C.
 #include "common.h"
+#include "../../include/cmda_hip_ext8.h"
 
 namespace {
 
@@ -462,6 +463,34 @@ extern "C" int cmda_bn_train_bwd(const void* dy, const void* x, const float* mea
     CMDA_LAUNCH(bn_fold_kernel, dim3((2 * C + 255) / 256, 1, groups), dim3(256), 0, stream, ws, 2 * C);
     CMDA_LAUNCH((bn_bwd_apply_kernel<T>), agrid, dim3(256), 0, stream, (const T*)dy + coff, (const T*)x, mean, rstd, gamma, beta,
                 ws + (long)kBnSlots * 2 * C, (T*)dx, dgamma, dbeta, (long)M, C, relu, lddy, 0, arpb);
+  });
+  CMDA_CHECK_LAUNCH();
+}
+
+// the statistics half of cmda_bn_train_fwd (its reduce, then its finalize with the running-statistic update), no apply: BatchNorm 2
+// of a ResNet BasicBlock, whose normalisation happens inside cmdax8_resavg_fwd (resblock.hip).  Declared in cmda_hip_ext8.h.
+extern "C" int cmdax8_bn_stats(const void* x, float* mean, float* rstd, float* running_mean, float* running_var, float* ws, int64_t M,
+                               int C, float eps, float momentum, int groups, const int* order, int ws_has_stats, int dtype,
+                               void* stream) {
+  if (M <= 0 || C <= 0) return CMDA_OK;
+  if ((C & 3) || groups < 1 || groups > 8) return CMDA_ERR_SHAPE;
+  BnOrder ord;
+  for (int i = 0; i < 8; ++i) ord.g[i] = (order && i < groups) ? order[i] : i;
+  unsigned seen = 0;
+  for (int i = 0; i < groups; ++i) {
+    if (ord.g[i] < 0 || ord.g[i] >= groups) return CMDA_ERR_SHAPE;
+    seen |= 1u << ord.g[i];
+  }
+  if (ws_has_stats && seen != (1u << groups) - 1u) return CMDA_ERR_SHAPE;   // (a repeated group would leave sums behind: cmda_bn_train_fwd)
+  if (dtype != CMDA_F32 && dtype != CMDA_BF16) return CMDA_ERR_DTYPE;
+  if (!ws_has_stats) cmda_zero_async(ws, sizeof(float) * (size_t)groups * (kBnSlots + 1) * 2 * C, stream);
+  const int gx = (C / 4 + 63) / 64;
+  const int rpb = rows_per_block(M * groups, gx);
+  dim3 rgrid(gx, (unsigned)((M + rpb - 1) / rpb), groups);
+  CMDA_DISPATCH_DTYPE(dtype, {
+    if (!ws_has_stats) CMDA_LAUNCH((bn_reduce_kernel<T>), rgrid, dim3(256), 0, stream, (const T*)x, ws, (long)M, C, rpb);
+    CMDA_LAUNCH((bn_finalize_kernel<T>), dim3((C + 7) / 8), dim3(256), 0, stream, (const T*)x, ws, mean, rstd,
+                running_mean, running_var, (long)M, C, eps, momentum, groups, ord, ws_has_stats);
   });
   CMDA_CHECK_LAUNCH();
 }

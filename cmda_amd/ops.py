@@ -1549,3 +1549,84 @@ def ohem_weight(logits, label, H, W, thresh, min_kept, ignore_index=255, debug=F
     first = L.lib().cmdax7_ws_bytes(0) // 4
     keys = ws[first:first + n].view(torch.float32).view(B, H, W)
     return weight, keys, thr_out
+
+
+# ---------------------------------------------------------------------------------------------- eighth ABI table (cmda_hip_ext8.h)
+_RES_BRANCHES = ('image', 'events')
+
+
+def _resavg_levels(levels, groups, backward):
+    """levels: per feature level dict(image=branch, events=branch, M=rows per group, C=channels, out= (forward) / dout= (backward)),
+    branch = dict(z, x, mean, rstd, gamma, beta) (+ dgamma, dbeta in the backward).  Returns (descriptor array, tensors kept alive,
+    the per-level ((dz, dres), (dz, dres)) of the backward)"""
+    if not 1 <= len(levels) <= 4:
+        raise L.CmdaError(f'resavg: 1 to 4 levels, got {len(levels)}')
+    arr = (L.Level8 * len(levels))()
+    keep, grads = [], []
+    first = levels[0]['image']['z']
+    for d, lv in zip(arr, levels):
+        M, C = int(lv['M']), int(lv['C'])
+        io = lv['dout' if backward else 'out']
+        maps = [io]
+        pair = []
+        for b, name in zip(d.br, _RES_BRANCHES):
+            br = lv[name]
+            maps += [br['z'], br['x']]
+            stats = [br['mean'], br['rstd'], br['gamma'], br['beta']] + ([br['dgamma'], br['dbeta']] if backward else [])
+            check_dev(*stats)
+            if any(t.dtype != torch.float32 for t in stats) or br['mean'].numel() != groups * C or br['rstd'].numel() != groups * C \
+                    or any(t.numel() != C for t in stats[2:]):
+                raise L.CmdaError('resavg: mean / rstd fp32 [groups, C], gamma / beta (and their gradients) fp32 [C]')
+            b.z, b.x, b.mean, b.rstd, b.gamma, b.beta = (t.data_ptr() for t in (br['z'], br['x'], *stats[:4]))
+            if backward:
+                dz, dres = torch.empty_like(br['z']), torch.empty_like(br['z'])
+                b.dz, b.dres, b.dgamma, b.dbeta = dz.data_ptr(), dres.data_ptr(), br['dgamma'].data_ptr(), br['dbeta'].data_ptr()
+                pair.append((dz, dres))
+                keep += [dz, dres]
+            keep += stats
+        check_dev(*maps)
+        if any(t.dtype != first.dtype or t.numel() != groups * M * C for t in maps):
+            raise L.CmdaError(f'resavg: every map holds groups*M*C = {groups * M * C} elements of one storage type')
+        if backward:
+            d.dout = io.data_ptr()
+        else:
+            d.out = io.data_ptr()
+        d.M, d.C = M, C
+        keep += maps
+        grads.append(tuple(pair))
+    return arr, keep, grads
+
+
+def resavg_fwd(levels, groups=1):
+    """cmdax8_resavg_fwd: lv['out'] = 0.5 * (relu(bn_i(z_i) + x_i) + relu(bn_e(z_e) + x_e)) for up to four levels in ONE launch;
+    rows [g*M, (g+1)*M) of a level use row g of mean / rstd.  `out` may be a row slice of a larger buffer.  Returns the outs."""
+    arr, keep, _ = _resavg_levels(levels, groups, False)
+    first = levels[0]['image']['z']
+    call('cmdax8_resavg_fwd', arr, c_i32(len(levels)), c_i32(groups), dtype_tag(first), stream_of(first))
+    return [lv['out'] for lv in levels]
+
+
+def resavg_bwd(levels, groups=1):
+    """cmdax8_resavg_bwd (one reducing and one applying launch for all levels, masks recomputed): per level
+    ((dz_image, dres_image), (dz_events, dres_events)); dgamma / dbeta of every branch are added into."""
+    arr, keep, grads = _resavg_levels(levels, groups, True)
+    first = levels[0]['image']['z']
+    n = L.lib().cmdax8_ws_floats(arr, len(levels), groups)
+    if n < 0:
+        raise L.CmdaError('cmdax8_ws_floats: bad shape')
+    ws = torch.empty(n, dtype=torch.float32, device=first.device)
+    call('cmdax8_resavg_bwd', arr, c_i32(len(levels)), c_i32(groups), ptr(ws), dtype_tag(first), stream_of(first))
+    return grads
+
+
+def bn_stats(x, running_mean, running_var, M, C, eps, momentum, groups=1, order=None, stats_ws=None):
+    """cmdax8_bn_stats: the statistics half of bn_train_fwd (same M = rows PER GROUP, groups, order, stats_ws): mean, rstd
+    [groups, C], running statistics (may be None) updated; no map is written"""
+    check_dev(x, running_mean, running_var, stats_ws)
+    mean = torch.empty(groups, C, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(groups, C, dtype=torch.float32, device=x.device)
+    ws = stats_ws if stats_ws is not None else torch.empty(groups * L.lib().cmda_bn_ws_floats(C), dtype=torch.float32, device=x.device)
+    order_c = (ctypes.c_int * groups)(*order) if order is not None else None
+    call('cmdax8_bn_stats', ptr(x), ptr(mean), ptr(rstd), ptr(running_mean), ptr(running_var), ptr(ws), c_i64(M), c_i32(C), c_f32(eps),
+         c_f32(momentum), c_i32(groups), order_c, c_i32(int(stats_ws is not None)), dtype_tag(x), stream_of(x))
+    return mean, rstd

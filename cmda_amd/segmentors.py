@@ -578,7 +578,10 @@ class FusionEncoderDecoder(nn.Module):
         f_image, sv_i = self.backbone_image.fwd(image, save=save, out_feats=[J[:m] for J, m in zip(joint, n)])
         rt.join_lanes('enc')
         f_events = [(J[2 * m:3 * m], h, w) for J, m, (h, w) in zip(joint, n, shapes)]
-        _, sv_f = self.fusion_module.fwd(f_image, f_events, B, save, into=[J[m:2 * m] for J, m in zip(joint, n)])
+        # a module with BatchNorm (`per_pass_statistics`) normalises each pass's rows with that pass's statistics and updates its
+        # running statistics pass after pass, as the reference's one call per forward does: it is told the number of passes
+        per_pass = dict(groups=len(image)) if getattr(self.fusion_module, 'per_pass_statistics', False) else {}
+        _, sv_f = self.fusion_module.fwd(f_image, f_events, B, save, into=[J[m:2 * m] for J, m in zip(joint, n)], **per_pass)
         feats = [(J, h, w) for J, (h, w) in zip(joint, shapes)]
         return feats, names, (sv_i, sv_e, sv_f, n, G), B
 
