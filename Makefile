@@ -14,7 +14,7 @@ all: hip emu
 hip: cmda_amd/libcmda_hip.so
 emu: tests/emu/libcmda_emu.so
 
-HDRS      := $(wildcard $(CSRC)/*.h) include/cmda_hip.h include/cmda_hip_ext.h include/cmda_hip_ext2.h include/cmda_hip_ext3.h include/cmda_hip_ext4.h include/cmda_hip_ext5.h include/cmda_hip_ext6.h include/cmda_hip_ext7.h include/cmda_hip_ext8.h
+HDRS      := $(wildcard $(CSRC)/*.h) include/cmda_hip.h include/cmda_hip_ext.h include/cmda_hip_ext2.h include/cmda_hip_ext3.h include/cmda_hip_ext4.h include/cmda_hip_ext5.h include/cmda_hip_ext6.h include/cmda_hip_ext7.h include/cmda_hip_ext8.h include/cmda_hip_ext9.h
 build/hip/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p build/hip
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@

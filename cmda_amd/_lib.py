@@ -1,6 +1,6 @@
 """ctypes binding of libcmda_hip.so (the C ABI declared in include/cmda_hip.h and its extensions include/cmda_hip_ext.h,
 include/cmda_hip_ext2.h, include/cmda_hip_ext3.h, include/cmda_hip_ext4.h, include/cmda_hip_ext5.h, include/cmda_hip_ext6.h,
-include/cmda_hip_ext7.h and include/cmda_hip_ext8.h).
+include/cmda_hip_ext7.h, include/cmda_hip_ext8.h and include/cmda_hip_ext9.h).
 
 The product path has exactly one backend: the gfx950 kernel library built in-tree by
 ``__graft_entry__.build()`` / ``make hip``.  If it is missing, or a tensor is not on the GPU,
@@ -29,6 +29,7 @@ ABI_EXT5_VERSION = 1
 ABI_EXT6_VERSION = 1
 ABI_EXT7_VERSION = 1
 ABI_EXT8_VERSION = 1
+ABI_EXT9_VERSION = 1
 
 
 class View(ctypes.Structure):
@@ -56,6 +57,11 @@ class Branch8(ctypes.Structure):   # cmdax8_branch_t
 
 class Level8(ctypes.Structure):    # cmdax8_level_t
     _fields_ = [('br', Branch8 * 2), ('out', c_vp), ('dout', c_vp), ('M', c_i64), ('C', c_i32), ('reserved', c_i32)]
+
+
+class Level9(ctypes.Structure):    # cmdax9_level_t
+    _fields_ = [('a', c_vp), ('b', c_vp), ('grad', c_vp), ('R', c_i64), ('lda', c_i64), ('ldb', c_i64), ('ldg', c_i64),
+                ('C', c_i32), ('reserved', c_i32)]
 
 
 class CmdaError(RuntimeError):
@@ -145,6 +151,19 @@ def _declare_ext8(lib):
     return lib
 
 
+def _declare_ext9(lib):
+    """the ninth table (include/cmda_hip_ext9.h): the feature-consistency loss.  Checked apart like the eighth; `_load` and
+    `_bind_for_tests` call it around `_declare_ext8(_declare(...))`."""
+    if not hasattr(lib, 'cmdax9_abi_version'):
+        raise CmdaError('the kernel library lacks the ninth ABI table (cmdax9_*): rebuild it')
+    lib.cmdax9_abi_version.restype = ctypes.c_int
+    if lib.cmdax9_abi_version() != ABI_EXT9_VERSION:
+        raise CmdaError('libcmda_hip.so ninth ABI table (cmdax9_*) version mismatch')
+    lib.cmdax9_ws_floats.restype = ctypes.c_int64
+    lib.cmdax9_ws_floats.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+    return lib
+
+
 def _load():
     global _lib
     if _lib is not None:
@@ -154,7 +173,7 @@ def _load():
             f'{_LIB_PATH} not found: build the gfx950 kernel library first '
             '(python -c "import __graft_entry__ as g; g.build()" or `make hip`). '
             'cmda_amd has no CPU fallback.')
-    _lib = _declare_ext8(_declare(ctypes.CDLL(_LIB_PATH)))
+    _lib = _declare_ext9(_declare_ext8(_declare(ctypes.CDLL(_LIB_PATH))))
     if _lib.cmda_abi_version() != ABI_VERSION:
         raise CmdaError('libcmda_hip.so ABI version mismatch')
     return _lib
@@ -163,7 +182,7 @@ def _load():
 def _bind_for_tests(path):
     """TEST ONLY: route the C ABI to the CPU emulator build of the same kernel sources."""
     global _lib, _emulated
-    _lib = _declare_ext8(_declare(ctypes.CDLL(path)))
+    _lib = _declare_ext9(_declare_ext8(_declare(ctypes.CDLL(path))))
     _emulated = True
     return _lib
 

@@ -7,6 +7,7 @@
 // The cross-workgroup totals (masked-cell count, loss) are taken by the LAST workgroup to finish (an integer ticket in a
 // caller-owned int32 that is zero before the launch and zero again after it), summing the per-row partials in index order.
 #include "common.h"
+#include "../../include/cmda_hip_ext9.h"
 
 namespace {
 
@@ -202,6 +203,195 @@ __global__ __launch_bounds__(64 * kFdRowWaves) void fdist_fwd_bwd_kernel(
   }
 }
 
+// ---- feature-consistency loss (include/cmda_hip_ext9.h; encoder_decoder.py:833-848) ---------------------------------------------
+// Every level is cut into 16-byte pieces of its rows (V elements; the last piece of a row is short when C % V != 0) and those into
+// chunks of kFcThreads * kFcPieces consecutive pieces (kFcPieces per thread, all loads of a chunk in flight at once).  A workgroup
+// works on ONE level, chunk wg, wg + nwg, ... of it; the grid is the sum of the levels' workgroups, about kFcGrid in all and shared
+// out in proportion to the levels' chunks, so the largest level does not serialise behind a fixed per-level grid.  The grid is kept
+// near one workgroup per CU because the arrival ticket is one atomic per workgroup on one address (~22 ns each on the MI355X: at a
+// workgroup per chunk, ~500 of them at the step's bf16 sizes, the tickets alone took twice the time of the streaming).
+constexpr int kFcThreads = 512;
+constexpr int kFcPieces = 4;
+constexpr int kFcGrid = 256;
+
+struct FcLevel {
+  const void* a;
+  const void* b;
+  void* g;
+  long lda, ldb, ldg;
+  unsigned pieces;   // R * ppr
+  unsigned ppr;      // pieces per row, ceil(C / V)
+  int C;
+  int wg0;           // the level's first workgroup
+  int nwg;           // the level's workgroups
+  int vec;           // base pointers and row strides keep every full piece 16-byte aligned
+  float inv_n;       // 1 / (R * C)
+};
+struct FcArgs {
+  FcLevel lv[CMDAX9_MAX_LEVELS];
+  int n;
+};
+
+// lambda * mean((a - b)^2) per level and its gradient ADDED into the level's block; the modes follow the pointers (loss == nullptr:
+// gradient only -- no partial, no ticket; lv.g == nullptr: no gradient for that level).
+template <typename T, typename G>
+__global__ __launch_bounds__(kFcThreads) void feat_consis_kernel(FcArgs args, float lambda, const float* __restrict__ gscale_ptr,
+                                                                float* __restrict__ loss, float* __restrict__ level_loss,
+                                                                int* __restrict__ ticket, float* __restrict__ partials) {
+  constexpr int V = sizeof(T) == 2 ? 8 : 4;
+  __shared__ float s_wave[kFcThreads / 64];
+  __shared__ float s_level[CMDAX9_MAX_LEVELS];
+  __shared__ int s_flag[1];
+  int l = 0;
+#pragma unroll
+  for (int k = 1; k < CMDAX9_MAX_LEVELS; ++k)
+    if (k < args.n && (int)blockIdx.x >= args.lv[k].wg0) l = k;
+  const FcLevel& lv = args.lv[l];
+  const T* __restrict__ a = (const T*)lv.a;
+  const T* __restrict__ b = (const T*)lv.b;
+  G* __restrict__ g = (G*)lv.g;
+  const float coef = g != nullptr ? (gscale_ptr != nullptr ? gscale_ptr[0] : 1.f) * lambda * (2.f * lv.inv_n) : 0.f;
+  constexpr unsigned kChunk = kFcThreads * kFcPieces;
+  const unsigned chunks = (lv.pieces + kChunk - 1) / kChunk;
+  float ss = 0.f;
+  for (unsigned chunk = (unsigned)blockIdx.x - (unsigned)lv.wg0; chunk < chunks; chunk += (unsigned)lv.nwg) {
+  const unsigned p0 = chunk * kChunk + threadIdx.x;
+  if (lv.vec && lv.C % V == 0) {   // every piece of the level is a full, aligned 16 bytes: the loads of all pieces first
+    float x[kFcPieces][8], y[kFcPieces][8];
+    long og[kFcPieces];
+    bool in[kFcPieces];
+#pragma unroll
+    for (int k = 0; k < kFcPieces; ++k) {
+      const unsigned p = p0 + (unsigned)(k * kFcThreads);
+      in[k] = p < lv.pieces;
+      const unsigned row = in[k] ? p / lv.ppr : 0u;
+      const long col = (long)(in[k] ? p - row * lv.ppr : 0u) * V;
+      og[k] = (long)row * lv.ldg + col;
+      if (in[k]) {
+        ldv<V>(a + ((long)row * lv.lda + col), x[k]);
+        ldv<V>(b + ((long)row * lv.ldb + col), y[k]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kFcPieces; ++k) {
+      if (!in[k]) continue;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        x[k][j] -= y[k][j];
+        ss = fmaf(x[k][j], x[k][j], ss);
+      }
+      if (g != nullptr) {
+        float z[8];
+        ldv<V>(g + og[k], z);
+#pragma unroll
+        for (int j = 0; j < V; ++j) z[j] = fmaf(coef, x[k][j], z[j]);
+        stv<V>(g + og[k], z);
+      }
+    }
+  } else {
+    for (int k = 0; k < kFcPieces; ++k) {
+      const unsigned p = p0 + (unsigned)(k * kFcThreads);
+      if (p >= lv.pieces) break;
+      const unsigned row = p / lv.ppr;
+      const int col = (int)(p - row * lv.ppr) * V;
+      const T* pa = a + ((long)row * lv.lda + col);
+      const T* pb = b + ((long)row * lv.ldb + col);
+      G* pg = g != nullptr ? g + ((long)row * lv.ldg + col) : nullptr;
+      if (lv.vec && col + V <= lv.C) {
+        float x[8], y[8];
+        ldv<V>(pa, x);
+        ldv<V>(pb, y);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+          x[j] -= y[j];
+          ss = fmaf(x[j], x[j], ss);
+        }
+        if (pg != nullptr) {
+          float z[8];
+          ldv<V>(pg, z);
+#pragma unroll
+          for (int j = 0; j < V; ++j) z[j] = fmaf(coef, x[j], z[j]);
+          stv<V>(pg, z);
+        }
+      } else {   // the short piece at the end of a row, or a level whose pointers / strides break the alignment
+        const int m = lv.C - col < V ? lv.C - col : V;
+        for (int j = 0; j < m; ++j) {
+          const float d = ldf(pa + j) - ldf(pb + j);
+          ss = fmaf(d, d, ss);
+          if (pg != nullptr) stf(pg + j, fmaf(coef, d, ldf(pg + j)));
+        }
+      }
+    }
+  }
+  }
+  if (loss == nullptr) return;   // gradient only (uniform over the grid)
+  ss = wave_sum(ss);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = ss;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int k = 0; k < kFcThreads / 64; ++k) t += s_wave[k];
+    partials[blockIdx.x] = t;
+  }
+  if (!last_group(ticket, &s_flag[0])) return;
+  for (int k = 0; k < args.n; ++k) {   // per level: strided sums, butterfly over the wave, the waves in order -- a fixed order
+    const int w0 = args.lv[k].wg0, w1 = k + 1 < args.n ? args.lv[k + 1].wg0 : (int)gridDim.x;
+    float t = 0.f;
+    for (int i = w0 + (int)threadIdx.x; i < w1; i += kFcThreads) t += partials[i];
+    t = wave_sum(t);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float tot = 0.f;
+      for (int i = 0; i < kFcThreads / 64; ++i) tot += s_wave[i];
+      s_level[k] = lambda * (tot * args.lv[k].inv_n);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    float tot = 0.f;
+    for (int k = 0; k < args.n; ++k) {
+      if (level_loss != nullptr) level_loss[k] = s_level[k];
+      tot += s_level[k];
+    }
+    loss[0] = tot;
+  }
+}
+
+// host side of cmdax9_*: the shape refusals and the cut of the levels into workgroups (piece: elements per 16 bytes of features)
+static int fc_plan(const cmdax9_level_t* levels, int n_levels, int piece, bool strides, FcArgs* out, long* grid) {
+  if (n_levels < 1 || n_levels > CMDAX9_MAX_LEVELS) return CMDA_ERR_SHAPE;
+  if (levels == nullptr) return CMDA_ERR_UNSUPPORTED;
+  long wg = 0, total = 0, chunks[CMDAX9_MAX_LEVELS];
+  for (int l = 0; l < n_levels; ++l) {
+    const cmdax9_level_t& d = levels[l];
+    if (d.R < 1 || d.C < 1) return CMDA_ERR_SHAPE;
+    if (strides && (d.lda < d.C || d.ldb < d.C || (d.grad != nullptr && d.ldg < d.C))) return CMDA_ERR_SHAPE;
+    const long ppr = ((long)d.C + piece - 1) / piece;
+    if (d.R > 0x7fffffffL / ppr) return CMDA_ERR_SHAPE;
+    const long pieces = d.R * ppr;
+    if (out != nullptr) {
+      FcLevel& k = out->lv[l];
+      k.a = d.a, k.b = d.b, k.g = d.grad;
+      k.lda = d.lda, k.ldb = d.ldb, k.ldg = d.ldg;
+      k.pieces = (unsigned)pieces, k.ppr = (unsigned)ppr, k.C = d.C;
+      k.inv_n = (float)(1.0 / ((double)d.R * (double)d.C));
+    }
+    chunks[l] = (pieces + kFcThreads * kFcPieces - 1) / (kFcThreads * kFcPieces);
+    total += chunks[l];
+  }
+  // the levels' shares of about kFcGrid workgroups, at least one each and never more than a level has chunks
+  for (int l = 0; l < n_levels; ++l) {
+    long n = total <= kFcGrid ? chunks[l] : (chunks[l] * kFcGrid + total - 1) / total;
+    n = n < 1 ? 1 : (n > chunks[l] ? chunks[l] : n);
+    if (out != nullptr) out->lv[l].wg0 = (int)wg, out->lv[l].nwg = (int)n;
+    wg += n;
+  }
+  if (out != nullptr) out->n = n_levels;
+  *grid = wg;
+  return CMDA_OK;
+}
+
 }  // namespace
 
 extern "C" int cmda_fdist_label_mask(const int64_t* label, int B, int H, int W, int h, int w, int nc, int ignore_index,
@@ -233,5 +423,44 @@ extern "C" int cmda_fdist_fwd_bwd(const void* fs, const void* ft, const uint8_t*
   else if (dtype == CMDA_BF16 && grad_dtype == CMDA_F32) CMDA_FD_LAUNCH(bf16_t, float);
   else return CMDA_ERR_DTYPE;
 #undef CMDA_FD_LAUNCH
+  CMDA_CHECK_LAUNCH();
+}
+
+extern "C" int cmdax9_abi_version(void) { return 1; }
+
+extern "C" int64_t cmdax9_ws_floats(const cmdax9_level_t* levels, int n_levels, int feat_dtype) {
+  if (feat_dtype != CMDA_F32 && feat_dtype != CMDA_BF16) return -1;
+  long grid = 0;
+  return fc_plan(levels, n_levels, feat_dtype == CMDA_BF16 ? 8 : 4, false, nullptr, &grid) == CMDA_OK ? (int64_t)grid : -1;
+}
+
+extern "C" int cmdax9_feat_consis(const cmdax9_level_t* levels, int n_levels, float lambda, const float* gscale, float* loss,
+                                  float* level_loss, int* ticket, float* partials_ws, int feat_dtype, int grad_dtype, void* stream) {
+  FcArgs args;
+  long grid = 0;
+  const bool tags = (feat_dtype == CMDA_F32 || feat_dtype == CMDA_BF16) && (grad_dtype == CMDA_F32 || grad_dtype == CMDA_BF16);
+  const int rc = fc_plan(levels, n_levels, feat_dtype == CMDA_BF16 ? 8 : 4, true, &args, &grid);
+  if (rc == CMDA_ERR_SHAPE) return rc;
+  if (!tags || (feat_dtype == CMDA_F32 && grad_dtype == CMDA_BF16)) return CMDA_ERR_DTYPE;
+  if (rc != CMDA_OK) return rc;
+  bool any_grad = false;
+  const size_t fsz = feat_dtype == CMDA_BF16 ? 2 : 4, gsz = grad_dtype == CMDA_BF16 ? 2 : 4;
+  for (int l = 0; l < n_levels; ++l) {
+    FcLevel& k = args.lv[l];
+    if (k.a == nullptr || k.b == nullptr) return CMDA_ERR_UNSUPPORTED;
+    any_grad = any_grad || k.g != nullptr;
+    bool vec = ((uintptr_t)k.a | (uintptr_t)k.b | (uintptr_t)(k.lda * fsz) | (uintptr_t)(k.ldb * fsz)) % 16 == 0;
+    if (k.g != nullptr) vec = vec && ((uintptr_t)k.g | (uintptr_t)(k.ldg * gsz)) % 16 == 0;
+    k.vec = vec ? 1 : 0;
+  }
+  if (loss == nullptr && !any_grad) return CMDA_ERR_UNSUPPORTED;
+  if (loss != nullptr && (ticket == nullptr || partials_ws == nullptr)) return CMDA_ERR_UNSUPPORTED;
+#define CMDA_FC_LAUNCH(T, G)                                                                                              \
+  CMDA_LAUNCH((feat_consis_kernel<T, G>), dim3((unsigned)grid), dim3(kFcThreads), 0, stream, args, lambda, gscale, loss, \
+              level_loss, ticket, partials_ws)
+  if (feat_dtype == CMDA_F32) CMDA_FC_LAUNCH(float, float);
+  else if (grad_dtype == CMDA_BF16) CMDA_FC_LAUNCH(bf16_t, bf16_t);
+  else CMDA_FC_LAUNCH(bf16_t, float);
+#undef CMDA_FC_LAUNCH
   CMDA_CHECK_LAUNCH();
 }

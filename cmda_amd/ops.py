@@ -834,6 +834,53 @@ def fdist_fwd_bwd(fs, ft, lam, mask=None, count=None, gscale=None, grad=None):
     return loss, norms
 
 
+def feat_consis(levels_a, levels_b, lam, gscale=None, grads=None, want_loss=True):
+    """The feature-consistency loss of the `isr_no_fusion` route (encoder_decoder.py:833-848): sum over the levels of
+    lam * F.mse_loss(a_l, b_l.detach()), and its gradient with respect to a_l ADDED into grads[l] -- every level in ONE launch.
+    levels_a / levels_b: 1 to 4 pairs of rows [R_l, C_l] in the compute dtype (unit column stride, any row stride: blocks of wider
+    buffers are fine); gscale: fp32 [1] device scale of the gradient (None: 1); grads: None (loss only), or one entry per level, each
+    None or an [R_l, C_l] block (row stride grads[l].stride(0)) of the features' dtype (or fp32 under bf16 features; one dtype for
+    all).  want_loss=False: gradient only.
+    Returns (loss fp32 [1], level_loss fp32 [n_levels]), or (None, None) when want_loss is False."""
+    n = len(levels_a)
+    assert n == len(levels_b) and (grads is None or len(grads) == n)
+    grads = list(grads) if grads is not None else [None] * n
+    given = [g for g in grads if g is not None]
+    if n < 1 or n > 4:
+        raise L.CmdaError(f'feat_consis: {n} levels (1 to 4)')
+    if not want_loss and not given:
+        raise L.CmdaError('feat_consis: neither the loss nor a gradient block is asked for')
+    first = levels_a[0]
+    dev = first.device
+    for t in (gscale, *levels_a, *levels_b, *given):
+        if t is None:
+            continue
+        if L.emulated() == t.is_cuda:
+            raise L.CmdaError('feat_consis: tensor on the wrong device')
+    if gscale is not None:
+        check_dev(gscale)
+    arr = (L.Level9 * n)()
+    for d, a, b, g in zip(arr, levels_a, levels_b, grads):
+        assert a.dim() == 2 and a.shape == b.shape and a.dtype == b.dtype == first.dtype and a.stride(1) == 1 and b.stride(1) == 1
+        d.a, d.b, d.R, d.C, d.lda, d.ldb = a.data_ptr(), b.data_ptr(), a.shape[0], a.shape[1], a.stride(0), b.stride(0)
+        if g is not None:
+            assert g.shape == a.shape and g.stride(1) == 1 and g.dtype == given[0].dtype
+            d.grad, d.ldg = g.data_ptr(), g.stride(0)
+    ftag = dtype_tag(first)
+    loss = level_loss = ticket = ws = None
+    if want_loss:
+        loss = torch.empty(1, dtype=torch.float32, device=dev)
+        level_loss = torch.empty(n, dtype=torch.float32, device=dev)
+        ticket = _fd_ticket(dev, 2)
+        nws = int(L.lib().cmdax9_ws_floats(arr, n, ftag))
+        if nws < 0:
+            raise L.CmdaError('cmdax9_ws_floats failed: bad shape')
+        ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    call('cmdax9_feat_consis', arr, c_i32(n), c_f32(lam), ptr(gscale), ptr(loss), ptr(level_loss), ptr(ticket), ptr(ws),
+         c_i32(ftag), c_i32(dtype_tag(given[0]) if given else ftag), stream_of(first))
+    return loss, level_loss
+
+
 def pseudo_label(logits, H, W, thr, want_prob=True):
     check_dev(logits)
     B, h, w, nc = logits.shape

@@ -181,18 +181,26 @@ def _aug_labels(probs):
 
 
 class _TrainFn(torch.autograd.Function):
-    """loss = runner.train_fwd(...); backward(dloss) -> runner.train_bwd(saved, dloss)."""
+    """loss = runner.train_fwd(...); backward(dloss) -> runner.train_bwd(saved, dloss).  A pass with a feature-consistency term
+    (FusionEncoderDecoder, `no_fusion` route) returns (loss_seg, loss_feat_consis) and back-propagates each with its own incoming
+    gradient."""
 
     @staticmethod
     def forward(ctx, runner, anchor, args):
         loss, aux, saved = runner.train_fwd(*args)
         ctx.runner, ctx.saved = runner, saved
         ctx.aux = aux
-        return loss
+        extra = aux[0].get('loss_feat_consis') if isinstance(aux[0], dict) else None
+        ctx.two = extra is not None
+        return (loss, extra.view(())) if ctx.two else loss
 
     @staticmethod
-    def backward(ctx, dloss):
-        ctx.runner.train_bwd(ctx.saved, dloss.contiguous().float().view(1))
+    def backward(ctx, dloss, dextra=None):
+        g = dloss.contiguous().float().view(1)
+        if ctx.two:
+            ctx.runner.train_bwd(ctx.saved, g, fc_gscale=dextra.contiguous().float().view(1))
+        else:
+            ctx.runner.train_bwd(ctx.saved, g)
         ctx.saved = None
         return None, None, None
 
@@ -428,8 +436,8 @@ class _Capture:
         self.holder['aux'] = aux
         return loss, aux, saved
 
-    def train_bwd(self, saved, gscale):
-        return self.model.train_bwd(saved, gscale)
+    def train_bwd(self, saved, gscale, **kw):
+        return self.model.train_bwd(saved, gscale, **kw)
 
 
 def _sum_grads(a, b):
@@ -618,14 +626,46 @@ class FusionEncoderDecoder(nn.Module):
         rt.join_lanes('wgrad')
 
     # -- hand-scheduled training pass ---------------------------------------------------------------------------------
-    def train_fwd(self, inputs, gt, seg_weight, cfg):
+    def train_fwd(self, inputs, gt, seg_weight, cfg, defer_feat_consis=False):
+        """defer_feat_consis: leave the feature-consistency loss (`_feat_consis_on`) to `train_bwd(..., fc_sink=...)`, whose ONE launch
+        gives loss and gradient; by default `losses['loss_feat_consis']` is computed here (loss-only launch)"""
         if self._joint_ok(inputs['image'], inputs['events'], cfg):
             feats, names, sv, B = self._extract_joint(inputs['image'], inputs['events'], inputs.get('img_self_res'), True)
             losses, logits, sv_h = self.decode_head.fwd_train_joint(feats, names, B, gt, seg_weight, cfg)
             return losses['loss_seg'], (losses, logits, feats), ('joint', sv, sv_h, B)
         feats, sv, B = self._extract(inputs['image'], inputs['events'], inputs.get('img_self_res'), cfg, True)
         losses, logits, sv_h = self.decode_head.fwd_train(feats, B, gt, seg_weight, cfg)
-        return losses['loss_seg'], (losses, logits, feats), (sv, sv_h, B)
+        if not self._feat_consis_on(cfg):
+            return losses['loss_seg'], (losses, logits, feats), (sv, sv_h, B)
+        fc = ([f[0] for f in feats['f_image']], [f[0] for f in feats['f_events']], float(cfg['lambda_feature_consistency']))
+        if not defer_feat_consis:   # the loss-only launch; train_bwd then runs the gradient-only one
+            losses['loss_feat_consis'] = ops.feat_consis(*fc)[0].view(())
+        return losses['loss_seg'], (losses, logits, feats), (sv, sv_h, B, fc)
+
+    # -- feature-consistency loss of the `no_fusion` route (forward_train :822-823, :833-848) ------------------------------------
+    def _feat_consis_on(self, cfg):
+        """train type 'cs2dsec_image+events' with cfg['no_fusion']: lambda * mse_loss(f_image[i], f_events[i].detach()) over the four
+        levels joins the loss (f_events: the event encoder's features of the ISR, the second input on these iterations)"""
+        return self.train_type == 'cs2dsec_image+events' and bool((cfg or {}).get('no_fusion'))
+
+    @staticmethod
+    def _feat_consis_hook(fc, gscale, sink, inner):
+        """img_grad_hook: the term's gradient ADDED into the image encoder's four output gradients (the ISR features are detached) --
+        one launch; with `sink` the same launch gives the loss (sink(loss [1]), the DACS route), else it is the gradient-only one.
+        A level the head left without a gradient gets a zeroed block first.  `inner`: the caller's own hook, run in front."""
+        fa, fb, lam = fc
+
+        def hook(d_img):
+            if inner is not None:
+                inner(d_img)
+            given = [d for d in d_img if d is not None]
+            for i, a in enumerate(fa):
+                if d_img[i] is None:
+                    d_img[i] = torch.zeros_like(a, dtype=given[0].dtype if given else a.dtype)
+            loss, _ = ops.feat_consis(fa, fb, lam, gscale=gscale, grads=d_img, want_loss=sink is not None)
+            if sink is not None:
+                sink(loss)
+        return hook
 
     def train_fwd_passes(self, passes, cfg, before_head=None):
         """P training passes with the same weights as ONE pass over P*B samples (passes: list of (inputs, gt, seg_weight)): the
@@ -646,8 +686,9 @@ class FusionEncoderDecoder(nn.Module):
                                                                 [p[2] for p in passes], cfg, passes=P)
         return [(l['loss_seg'], l) for l in losses], ('joint', sv, sv_h, Bt, P, feats)
 
-    def train_bwd(self, saved, gscale, img_grad_hook=None):
-        """img_grad_hook: see _extract_joint_bwd (the image encoder's output gradients, before its backward pass)"""
+    def train_bwd(self, saved, gscale, img_grad_hook=None, fc_gscale=None, fc_sink=None):
+        """img_grad_hook: see _extract_joint_bwd (the image encoder's output gradients, before its backward pass).
+        fc_gscale: the incoming gradient of the feature-consistency loss (fp32 [1]; None: gscale); fc_sink: see `_feat_consis_hook`"""
         with ops.backward_scope():   # LayerNorm parameter gradients of the whole pass folded by one launch at the end
             if saved[0] == 'joint':
                 _, sv, sv_h, B = saved[:4]
@@ -675,7 +716,9 @@ class FusionEncoderDecoder(nn.Module):
                 self._extract_joint_bwd(sv, dJ, B, img_grad_hook=img_grad_hook)
                 rt.join_lanes('hw')
                 return
-            sv, sv_h, B = saved
+            sv, sv_h, B = saved[:3]
+            if len(saved) > 3:   # the feature-consistency term: the same hook point, behind the caller's hook
+                img_grad_hook = self._feat_consis_hook(saved[3], gscale if fc_gscale is None else fc_gscale, fc_sink, img_grad_hook)
             dfeats = self.decode_head.bwd_train(sv_h, B, gscale)
             rt.notify_grads_ready('decode_head', self.decode_head)
             self._extract_bwd(sv, dfeats, B, img_grad_hook=img_grad_hook)
@@ -689,7 +732,10 @@ class FusionEncoderDecoder(nn.Module):
         out = {}
         if return_feat:
             out['features'] = feats
-        out.update(add_prefix({'loss_seg': loss, 'acc_seg': losses['acc_seg']}, 'decode'))
+        if isinstance(loss, tuple):   # (loss_seg, loss_feat_consis): `_feat_consis_on`
+            out.update(add_prefix({'loss_seg': loss[0], 'loss_feat_consis': loss[1], 'acc_seg': losses['acc_seg']}, 'decode'))
+        else:
+            out.update(add_prefix({'loss_seg': loss, 'acc_seg': losses['acc_seg']}, 'decode'))
         pred = {k: (v.permute(0, 3, 1, 2) if v is not None else None) for k, v in logits.items()}
         return out, pred
 

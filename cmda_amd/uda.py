@@ -604,22 +604,35 @@ class DACS(nn.Module):
         `student.train_fwd`; keep_mix: what lane 'T' keeps alive for the mixed forward; rows4(saved, feats) -> the source pass's stage-4
         image rows (feature distance); join_fd: the feature-distance targets were made on lane 'T', which this route otherwise joins
         only behind the source backward."""
-        loss, (losses, _, feats_src), saved_src = student.train_fwd(*fwd_src)
+        # feature-consistency term of the `isr_no_fusion` route (encoder_decoder.py:822-823): loss and gradient come from ONE launch per
+        # pass, inside the backward pass (`fc_sink`), so the forward passes leave it alone
+        fc = len(fwd_src) > 3 and getattr(student, '_feat_consis_on', lambda cfg: False)(fwd_src[3])
+        kw = dict(defer_feat_consis=True) if fc else {}
+        loss, (losses, _, feats_src), saved_src = student.train_fwd(*fwd_src, **kw)
         log_vars['decode.loss_seg'], log_vars['decode.acc_seg'] = loss, losses['acc_seg']
         with rt.lane('T', *keep_mix):
-            loss, (losses, _, _), saved_mix = student.train_fwd(*fwd_mix)
+            loss, (losses, _, _), saved_mix = student.train_fwd(*fwd_mix, **kw)
         log_vars['mix.decode.loss_seg'], log_vars['mix.decode.acc_seg'] = loss, losses['acc_seg']
         log_vars['loss'] = loss   # _parse_losses of the mixed step overwrites 'loss' (dacs.py:851-857)
+        kw_src = kw_mix = {}
+        if fc:
+            def fc_src(l):
+                log_vars['decode.loss_feat_consis'] = l.view(())
+
+            def fc_mix(l, loss_seg=loss):   # _parse_losses sums every '*loss*' entry of the mixed step into 'loss'
+                log_vars['mix.decode.loss_feat_consis'] = l.view(())
+                log_vars['loss'] = ops.axpby(loss_seg.view(1), l, 1.0, 1.0).view(())
+            kw_src, kw_mix = dict(fc_sink=fc_src), dict(fc_sink=fc_mix)
         fd_hook = None
         if fd is not None:
             if join_fd:
                 rt.join_lanes('T')
             fd_hook = self._fdist_hook(fd, lambda: rows4(saved_src, feats_src), one, log_vars)
-        student.train_bwd(saved_src, one, img_grad_hook=fd_hook)
+        student.train_bwd(saved_src, one, img_grad_hook=fd_hook, **kw_src)
         del saved_src, feats_src
         rt.join_lanes('T')
         with self._last_backward(one.device):
-            student.train_bwd(saved_mix, one)
+            student.train_bwd(saved_mix, one, **kw_mix)
 
     @staticmethod
     def _with_fdist(extras, fd):
